@@ -11,13 +11,17 @@ config 4 — 8192 agents in total sharded over the N GPUs (1024 per GPU at N = 8
 --weak keeps 4096 agents per GPU instead. FoV (--workload fov): config 5's 512-agent per-GPU
 share at N = 1, its 4096 agents in total at N > 1.
 
-    python bench.py [--gpus N --steps K --warmup W]      (N > 1: relaunches itself as N ranks)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                                                         (N > 1: relaunches itself as N ranks)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Timing: the timed pass runs warm-up + K steps with nothing else on the stream (barrier +
-synchronize on both sides, max over ranks); an identical replay of the same steps (same initial
-swarm and counter-based noise) records HIP events around every step and every IMPC kernel for the
-p99 step latency and the kernel's average duration (roofline).
+synchronize on both sides, max over ranks). A plain run is that pass alone: it prints the result
+line (QP/s, ms_per_step, statuses) and, with --dump-outputs DIR, writes the last timed step's
+outputs as DIR/<name>.npy. --full adds everything else: an identical replay of the same steps (same
+initial swarm and counter-based noise) that records HIP events around every step and every IMPC
+kernel for the p99 step latency and the kernel's average duration (roofline), the closed-loop
+trace with its safety metrics, and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -83,8 +87,38 @@ def parse(argv=None):
     ap.add_argument("--no-trace", action="store_true",
                     help="skip the closed-loop safety metrics pass (collision_check.py on the trace)")
     ap.add_argument("--dump", default="",
-                    help="write the timed pass's per-step status / solver-step logs (rank 0) to this .npz")
+                    help="write the timed pass's per-step status / solver-step logs (rank 0) to this .npz "
+                         "(with --full also the replay's kernel times and the closed-loop state trace)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the event-timed replay (p99 step latency, "
+                         "kernel times, roofline), the closed-loop trace and its safety metrics, the CPU "
+                         "baseline; dense: the single-QP latencies and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what their last step computed (rank 0) as DIR/<name>.npy")
     return ap.parse_args(argv)
+
+
+DUMP_OUTPUTS_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every array as directory/<name>.npy, float64 kept and everything else as
+    float32. Beyond DUMP_OUTPUTS_MAX_BYTES in all, each array keeps a fixed seeded sample of its
+    rows (sorted indices, the same fraction of every array) instead. The library marks a value it
+    has none for with NaN (the objective of a QP that is not OPTIMAL, the curve of an agent that
+    has not had one yet): those are written as 0, so that the files hold finite numbers and
+    compare entry by entry; status.npy says which QPs have a solution. An infinity is kept."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    arrays = {k: np.where(np.isnan(v), 0, v).astype(v.dtype) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, v in arrays.items():
+        if total > DUMP_OUTPUTS_MAX_BYTES and v.ndim > 0 and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * 0.98 * DUMP_OUTPUTS_MAX_BYTES / total))
+            rows = np.sort(np.random.default_rng(20251015).choice(v.shape[0], size=keep, replace=False))
+            v = v[rows]
+        np.save(os.path.join(directory, name + ".npy"), v)
 
 
 def flops_per_qp(iters: np.ndarray, rows: np.ndarray, nz: int) -> float:
@@ -171,11 +205,14 @@ def run_dense(args) -> None:
     for _ in range(args.steps):
         call.run_raw()
     dt = time.perf_counter() - t0
-    st, xs, obj = call.run()
+    # the last timed call's outputs, as the caller's arrays hold them
+    st, obj = call.st[:batch].copy(), call.obj[:batch].copy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(status=st, obj=obj, x=np.stack(call.xs)))
     refb = ref[np.arange(batch) % count]
     rel = np.abs(obj - refb) / np.maximum(1.0, np.abs(refb))
     single = []
-    for q in qps:
+    for q in qps if args.full else []:
         t1 = time.perf_counter()
         s1, _, o1 = L.dense_qp_solve(**q)
         single.append(time.perf_counter() - t1)
@@ -186,10 +223,11 @@ def run_dense(args) -> None:
             "vs_baseline": None, "dtype": "f64", "data": "golden QPs (tests/golden/golden_qps.npz)",
             "config": {"workload": f"generic dense path: {batch} QPs per call ({count} golden MPC-CBF QPs "
                                    "replicated), n=36, 30 equalities, host arrays in/out"},
-            "status_hist": hist, "max_rel_obj_err_vs_golden": float(rel.max()),
-            "single_qp_latency_ms": {"median": 1e3 * float(np.median(single)),
-                                     "max": 1e3 * float(np.max(single))}}
-    if not args.no_cpu_baseline:
+            "status_hist": hist, "max_rel_obj_err_vs_golden": float(rel.max())}
+    if single:
+        line["single_qp_latency_ms"] = {"median": 1e3 * float(np.median(single)),
+                                        "max": 1e3 * float(np.max(single))}
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "tests"))
         import oracle_lib as O
         big_ = np.finfo(np.float64).max
@@ -292,6 +330,7 @@ def main():
 
     replay_same = None
     trace_res = None
+    last_outputs = None
     nb_lists = {}
     if args.neighbours == "all":  # every other robot, as the reference hands them to optimize()
         rp_all = np.arange(per + 1, dtype=np.int32) * (total - 1)
@@ -309,7 +348,7 @@ def main():
             dist.broadcast(uid, 0)
             comm = Comm(bytes(uid.cpu().tolist()), world, rank, local)
 
-        kc_waves = ctx.launch_waves(per)
+        kc_waves = ctx.launch_waves(per) if args.full else 0  # the replay's launch clock
         kclock = torch.zeros((nsteps, max(kc_waves, 1), 2), dtype=torch.int64, device=dev) if kc_waves else None
 
         def closed_loop(log, timing):
@@ -346,24 +385,32 @@ def main():
             return time.perf_counter() - t0, r
 
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        elapsed, _ = closed_loop(logs[0], timing=False)
+        elapsed, r0 = closed_loop(logs[0], timing=False)
         # device time of the timed region by HIP events at its two ends (no event between launches)
         region_ms = e0.elapsed_time(e1)
-        # replay of the identical steps (same initial swarm, counter-based noise keyed by the step
-        # index) with HIP events on the launch stream: per-step device time (p99), the events around
-        # every IMPC launch, and each launch's own duration on the device clock (first-wave start to
-        # last-wave end, s_memrealtime 100 MHz, mpccbf_run::kernel_clock; collision kernels only: the
-        # FoV kernels carry none) — the clock's per-wave stores cost ~0.6 us per launch, so the
-        # throughput pass carries neither
-        _, rr = closed_loop(logs[1], timing=True)
-        launch_us = None
-        if kclock is not None:
-            from mpccbf._lib import kernel_clock_us
-            launch_us = kernel_clock_us(kclock.cpu().numpy())
-            launch_us = launch_us if np.all(np.isfinite(launch_us)) else None
-        step_ms, kern_ms = rr["step_ms"].astype(np.float64), rr["solve_ms"].astype(np.float64)
-        replay_same = bool(torch.equal(logs[0][0], logs[1][0]) and torch.equal(logs[0][1], logs[1][1]))
-        if world == 1 and not args.no_trace and args.rank_share <= 0:
+        if args.dump_outputs and rank == 0 and nsteps > 0:
+            # what the caller holds after the last timed step: the kept curves and objectives, that
+            # step's statuses and solver steps, and the state table the step wrote (obj is NaN
+            # where an IMPC iteration was infeasible or not attempted: dump_outputs writes 0 there)
+            last_outputs = dict(x=out["x"].cpu().numpy(), obj=out["obj"].cpu().numpy(),
+                                status=logs[0][0][-1].cpu().numpy(), iters=logs[0][1][-1].cpu().numpy(),
+                                states=r0["final"].cpu().numpy())
+        step_ms = kern_ms = launch_us = None  # the replay's figures (--full)
+        if args.full:
+            # replay of the identical steps (same initial swarm, counter-based noise keyed by the step
+            # index) with HIP events on the launch stream: per-step device time (p99), the events around
+            # every IMPC launch, and each launch's own duration on the device clock (first-wave start to
+            # last-wave end, s_memrealtime 100 MHz, mpccbf_run::kernel_clock; collision kernels only: the
+            # FoV kernels carry none) — the clock's per-wave stores cost ~0.6 us per launch, so the
+            # throughput pass carries neither
+            _, rr = closed_loop(logs[1], timing=True)
+            if kclock is not None:
+                from mpccbf._lib import kernel_clock_us
+                launch_us = kernel_clock_us(kclock.cpu().numpy())
+                launch_us = launch_us if np.all(np.isfinite(launch_us)) else None
+            step_ms, kern_ms = rr["step_ms"].astype(np.float64), rr["solve_ms"].astype(np.float64)
+            replay_same = bool(torch.equal(logs[0][0], logs[1][0]) and torch.equal(logs[0][1], logs[1][1]))
+        if args.full and world == 1 and not args.no_trace and args.rank_share <= 0:
             # the same closed loop once more, one step per call, every step's state table kept:
             # the trace the reference's collision_check.py scores (outside the timed region)
             tables = [full0.clone(), torch.empty_like(full0)]
@@ -433,14 +480,22 @@ def main():
         kern_ms = np.array([a.elapsed_time(b) for a, b in kev])
         region_ms = None
         launch_us = None
+        if args.dump_outputs and rank == 0 and nsteps > 0:
+            last_outputs = dict(x=out["x"].cpu().numpy(), obj=out["obj"].cpu().numpy(),
+                                status=logs[0][0][-1].cpu().numpy(), iters=logs[0][1][-1].cpu().numpy(),
+                                states=shard.full.cpu().numpy())
 
+    if last_outputs is not None:
+        dump_outputs(args.dump_outputs, last_outputs)
     status = logs[0][0].cpu().numpy()
     iters = logs[0][1].cpu().numpy()
     if args.dump and rank == 0:
         extra = {}
         if trace_res is not None:  # every step's state table (warm-up steps first)
             extra = dict(traj=trace_res["traj"], warmup=args.warmup)
-        np.savez_compressed(args.dump, status=status, iters=iters, kernel_ms=np.asarray(kern_ms), **extra)
+        if kern_ms is not None:
+            extra["kernel_ms"] = np.asarray(kern_ms)
+        np.savez_compressed(args.dump, status=status, iters=iters, **extra)
     attempted = ~((status == 5) & (iters == 0))  # UNKNOWN with 0 steps: iteration not attempted
     hist = {name: int(np.sum((status == code) & attempted)) for code, name in STATUS_NAMES.items()}
     hist["not_attempted"] = int(np.sum(~attempted))
@@ -455,9 +510,12 @@ def main():
     newton_mean = att_it.sum(axis=(1, 2)) / np.maximum(attempted.sum(axis=(1, 2)), 1)
     newton_max = att_it.max(axis=(1, 2))
 
+    timed_kernels = kern_ms is not None  # per-step and per-kernel times: --full, or the host-driven loop
     vals = [elapsed, float(hist["OPTIMAL"]), float(hist["INFEASIBLE"]), float(hist["UNKNOWN"]),
-            float(hist["ERROR"]), float(hist["not_attempted"]), flops, float(np.mean(kern_ms)),
-            float(np.percentile(step_ms, 99)), float(np.max(kern_ms)), float(bool(replay_same) or replay_same is None),
+            float(hist["ERROR"]), float(hist["not_attempted"]), flops,
+            float(np.mean(kern_ms)) if timed_kernels else -1.0,
+            float(np.percentile(step_ms, 99)) if timed_kernels else -1.0,
+            float(np.max(kern_ms)) if timed_kernels else -1.0, float(bool(replay_same) or replay_same is None),
             float(np.mean(launch_us)) if launch_us is not None else -1.0,
             float(np.max(launch_us)) if launch_us is not None else -1.0]
     t = torch.tensor(vals, dtype=torch.float64, device=dev)
@@ -502,20 +560,6 @@ def main():
         solved = hist["OPTIMAL"] + hist["INFEASIBLE"]
         attempted_n = solved + hist["UNKNOWN"] + hist["ERROR"]
         qps = solved / elapsed
-        # roofline of the dominant kernel on rank 0: executed algorithmic flops per launch /
-        # average launch time (HIP events on the launch stream, every step of the replay)
-        flops_per_launch = flops_rank0 / nsteps
-        achieved_tf = flops_per_launch / (kern_avg * 1e-3) / 1e12
-        wl = ("fovs" if args.slack else "fov") if fov else "collision"
-        traffic, traffic_src = pmc_traffic(kname, wl)
-        # VALU issue: the kernel is bound by dependent-instruction latency at one wave per SIMD;
-        # wave-level VALU instructions per launch (PMC SQ_INSTS_VALU) / launch time against the
-        # issue peak (every SIMD one wave64 VALU op per 4 cycles: 1024 SIMDs x 2.4 GHz / 4)
-        valu_insts, valu_src = pmc_lookup(kname, wl, "SQ_INSTS_VALU")
-        abytes = algorithmic_bytes_per_agent(ctx.n, nbk, cfg["impc_iter"], cov is not None) * per
-        # every IMPC kernel is bound by its agents' dependent instruction chains (latency at one or
-        # a few waves per SIMD), not by MFMA, VALU throughput or HBM (the fractions below say how far)
-        bound = "latency"
         res = {
             "metric": "QP solves/sec (whole node) + p99 step latency, N-agent horizon-15 MPC-CBF",
             "value": qps,
@@ -524,7 +568,7 @@ def main():
             "steps": nsteps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / nsteps * 1e3,
-            "p99_step_ms": p99,
+            "p99_step_ms": p99 if timed_kernels else None,  # per-step events: --full (the replay)
             "higher_is_better": True,
             "scaling": "weak" if args.agents_total <= 0 else "strong",
             "vs_baseline": None,
@@ -565,10 +609,29 @@ def main():
             "status_hist": hist,
             "newton_steps_per_qp": ({"mean_by_step": [round(float(v), 3) for v in newton_mean],
                                      "max_by_step": [int(v) for v in newton_max],
-                                     "kernel_us_by_step": [round(float(v) * 1e3, 1) for v in kern_ms]}
+                                     "kernel_us_by_step": ([round(float(v) * 1e3, 1) for v in kern_ms]
+                                                           if timed_kernels else None)}
                                     if nsteps <= 64 else
                                     {"mean": float(np.mean(newton_mean)), "max": int(np.max(newton_max))}),
-            "roofline": {
+            "roofline": None,
+            "cpu_baseline": None,
+        }
+        if timed_kernels:
+            # roofline of the dominant kernel on rank 0: executed algorithmic flops per launch /
+            # average launch time (HIP events on the launch stream, every step of the replay)
+            flops_per_launch = flops_rank0 / nsteps
+            achieved_tf = flops_per_launch / (kern_avg * 1e-3) / 1e12
+            wl = ("fovs" if args.slack else "fov") if fov else "collision"
+            traffic, traffic_src = pmc_traffic(kname, wl)
+            # VALU issue: the kernel is bound by dependent-instruction latency at one wave per SIMD;
+            # wave-level VALU instructions per launch (PMC SQ_INSTS_VALU) / launch time against the
+            # issue peak (every SIMD one wave64 VALU op per 4 cycles: 1024 SIMDs x 2.4 GHz / 4)
+            valu_insts, valu_src = pmc_lookup(kname, wl, "SQ_INSTS_VALU")
+            abytes = algorithmic_bytes_per_agent(ctx.n, nbk, cfg["impc_iter"], cov is not None) * per
+            # every IMPC kernel is bound by its agents' dependent instruction chains (latency at one or
+            # a few waves per SIMD), not by MFMA, VALU throughput or HBM (the fractions below say how far)
+            bound = "latency"
+            res["roofline"] = {
                 "bound": bound,
                 "achieved": achieved_tf,
                 "peak": FP64_PEAK_TFLOPS,
@@ -606,37 +669,35 @@ def main():
                         "achieved_gbs": abytes / (kern_avg * 1e-3) / 1e9,
                         "peak_gbs": HBM_PEAK_GBS,
                         "frac": abytes / (kern_avg * 1e-3) / 1e9 / HBM_PEAK_GBS},
-            },
-            "cpu_baseline": None,
-        }
-        if replay_same is False:
-            res["roofline"]["kernel_timing"] += " (WARNING: replay statuses differ)"
-        occ, occ_src = resource_lookup(kname, "occupancy")
-        sq_wait, _ = pmc_lookup(kname, wl, "SQ_WAIT_ANY")
-        sq_cyc, sq_src = pmc_lookup(kname, wl, "SQ_WAVE_CYCLES")
-        res["roofline"]["occupancy_waves_per_simd"] = occ
-        res["roofline"]["occupancy_source"] = occ_src
-        res["roofline"]["sq_wait_frac"] = (sq_wait / sq_cyc) if (sq_wait is not None and sq_cyc) else None
-        res["roofline"]["sq_wait_source"] = sq_src
-        # FP64 the kernel issued (PMC: FMA x 2 + MUL + ADD + TRANS wave instructions x 64 lanes per
-        # launch) against the vector FP64 peak over the launch: what the hardware executed,
-        # assembly and outputs included, where `frac` counts the solver's algorithmic flops only
-        f64 = [pmc_lookup(kname, wl, c)[0] for c in ("SQ_INSTS_VALU_FMA_F64", "SQ_INSTS_VALU_MUL_F64",
-                                                      "SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_TRANS_F64")]
-        if all(v is not None for v in f64):
-            issued = (2 * f64[0] + f64[1] + f64[2] + f64[3]) * 64
-            res["roofline"]["fp64_issued"] = {
-                "flops_per_launch": issued, "achieved_tflops": issued / (kern_avg * 1e-3) / 1e12,
-                "frac": issued / (kern_avg * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
-                "source": pmc_lookup(kname, wl, "SQ_INSTS_VALU_FMA_F64")[1]}
-        # the launch against its longest agent chain (stamps build: setup .. outputs of the slowest
-        # agent, tools/stamp_profile.py): what a latency-bound launch cannot go below
-        cp = critical_path_lookup(kname, wl, per)
-        if cp is not None:
-            res["roofline"]["critical_path"] = cp
+            }
+            if replay_same is False:
+                res["roofline"]["kernel_timing"] += " (WARNING: replay statuses differ)"
+            occ, occ_src = resource_lookup(kname, "occupancy")
+            sq_wait, _ = pmc_lookup(kname, wl, "SQ_WAIT_ANY")
+            sq_cyc, sq_src = pmc_lookup(kname, wl, "SQ_WAVE_CYCLES")
+            res["roofline"]["occupancy_waves_per_simd"] = occ
+            res["roofline"]["occupancy_source"] = occ_src
+            res["roofline"]["sq_wait_frac"] = (sq_wait / sq_cyc) if (sq_wait is not None and sq_cyc) else None
+            res["roofline"]["sq_wait_source"] = sq_src
+            # FP64 the kernel issued (PMC: FMA x 2 + MUL + ADD + TRANS wave instructions x 64 lanes per
+            # launch) against the vector FP64 peak over the launch: what the hardware executed,
+            # assembly and outputs included, where `frac` counts the solver's algorithmic flops only
+            f64 = [pmc_lookup(kname, wl, c)[0] for c in ("SQ_INSTS_VALU_FMA_F64", "SQ_INSTS_VALU_MUL_F64",
+                                                          "SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_TRANS_F64")]
+            if all(v is not None for v in f64):
+                issued = (2 * f64[0] + f64[1] + f64[2] + f64[3]) * 64
+                res["roofline"]["fp64_issued"] = {
+                    "flops_per_launch": issued, "achieved_tflops": issued / (kern_avg * 1e-3) / 1e12,
+                    "frac": issued / (kern_avg * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
+                    "source": pmc_lookup(kname, wl, "SQ_INSTS_VALU_FMA_F64")[1]}
+            # the launch against its longest agent chain (stamps build: setup .. outputs of the slowest
+            # agent, tools/stamp_profile.py): what a latency-bound launch cannot go below
+            cp = critical_path_lookup(kname, wl, per)
+            if cp is not None:
+                res["roofline"]["critical_path"] = cp
         if trace_res is not None:
             res["closed_loop"] = closed_loop_metrics(trace_res, targets_h, cfg, fov)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(cfg, states_h, targets_h, args, radius, cov_h, trace_res)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 """Appends the two all-neighbour slack QPs that ended UNKNOWN in round 3 to regress_cases.json
 (collision controller, slack_mode, every other robot as a neighbour): step 100 agent 87 and step 143
-agent 52 of `bench.py --neighbours all --crowded --slack --steps 200 --warmup 20 --dump all256s.npz`
+agent 52 of `bench.py --full --neighbours all --crowded --slack --steps 200 --warmup 20 --dump all256s.npz`
 (256 agents; the dump's state table of that step). Row 0 = the ego, rows 1.. = every other robot in
 index order (its neighbour list). Round 3: GPU [OPTIMAL, UNKNOWN], oracle [UNKNOWN, UNKNOWN]; the
 oracle's exact presolves (box-implied slack rows dropped, idle slack columns fixed at 0) solve both.

@@ -81,3 +81,35 @@ def test_cpu_baseline_samples_timed_steps(bench, monkeypatch):
     assert len(cb["step_ms"]) == len(cb["steps_sampled"])
     assert cb["cores"] == min(2, cb["affinity_cpus"])
     assert cb["p99_step_ms"] <= max(cb["step_ms"]) + 1e-9 and cb["value"] > 0
+
+
+def test_plain_run_by_default(bench):
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs == ""
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays(bench, tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per array, float64 kept, integers as float32; past the size limit
+    every array keeps the same seeded row sample, identical from run to run."""
+    import numpy as np
+    arrays = dict(x=np.arange(600, dtype=np.float64).reshape(100, 6),
+                  status=np.arange(200, dtype=np.int32).reshape(100, 2))
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    x, st = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "status.npy")
+    assert x.dtype == np.float64 and st.dtype == np.float32
+    assert np.array_equal(x, arrays["x"]) and np.array_equal(st, arrays["status"])
+    # a value the library has none for (NaN) is written as 0: the files hold finite numbers
+    obj = np.array([[1.5, np.nan], [np.nan, -2.0]])
+    bench.dump_outputs(str(tmp_path / "n"), dict(obj=obj))
+    assert np.array_equal(np.load(tmp_path / "n" / "obj.npy"), [[1.5, 0.0], [0.0, -2.0]])
+    total = sum(v.nbytes for v in (x, st))
+    monkeypatch.setattr(bench, "DUMP_OUTPUTS_MAX_BYTES", total // 2)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    xb, sb = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "status.npy")
+    assert xb.nbytes + sb.nbytes <= total // 2 and 0 < xb.shape[0] == sb.shape[0] < 100
+    rows = (xb[:, 0] / 6).astype(int)
+    assert np.array_equal(xb, arrays["x"][rows]) and np.array_equal(sb, arrays["status"][rows])
+    assert np.array_equal(xb, np.load(tmp_path / "c" / "x.npy"))

@@ -2,7 +2,7 @@
 # A/B of the IMPC iteration-1 active-set warm start threshold (mpccbf_options.das_warm_steps) on the
 # driver's bench command and the 1000-step line; interleaved, two repetitions each.
 O=gpurun_out/${1:-ab_daswarm}; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-trace"
+B="python3 bench.py --full --no-cpu-baseline --no-trace"
 for r in 1 2; do
   for w in 0 2 1 -1; do
     timeout -k 10 200 $B --steps 20 --warmup 5 --das-warm $w > $O/drv_w${w}_r$r.json 2>/dev/null || exit 1

@@ -1,5 +1,5 @@
 """Offline study of the dual active-set (Goldfarb-Idnani) step counts on real QPs: for the agents a
-`bench.py --dump` (with the state trace) records, the oracle assembles IMPC iteration 0's QP, the
+`bench.py --full --dump` (with the state trace) records, the oracle assembles IMPC iteration 0's QP, the
 equalities are eliminated (null space), and the range-space dual active-set method of
 pdip_sep.hpp sep_dual_as runs in numpy with different candidate rules:
   scaled  — the device's rule: the largest violation scaled by 1 / (1 + |bound|)

@@ -1,4 +1,4 @@
-"""Re-solve the FoV (config 5) QPs of a `bench.py --workload fov --dump` trace on the GPU, once with
+"""Re-solve the FoV (config 5) QPs of a `bench.py --full --workload fov --dump` trace on the GPU, once with
 the default solver and once with the PDIP alone (mpccbf_options.dual_as_steps < 0), and list the agents whose
 default solve took many steps: which QPs the dual active set hands to the PDIP.
 

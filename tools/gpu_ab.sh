@@ -16,7 +16,7 @@ for r in 1 2; do
   i=0
   for e in "$@"; do
     echo "[$(date +%T)] $e $ARGS ($r)"
-    env $e timeout -k 10 200 python3 bench.py --no-cpu-baseline $ARGS > $O/${i}_$r.json 2> $O/${i}_$r.err
+    env $e timeout -k 10 200 python3 bench.py --full --no-cpu-baseline $ARGS > $O/${i}_$r.json 2> $O/${i}_$r.err
     i=$((i + 1))
   done
 done

@@ -13,7 +13,7 @@ O=$ROOT/gpurun_out/$TAG
 mkdir -p $O
 cd $ROOT
 step() { echo "[$(date +%T)] $*"; }
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
   step pytest
   timeout -k 10 500 python3 -u -m pytest tests -m gpu -q -x --timeout 200 --timeout-method thread > $O/pytest.log 2>&1
@@ -21,7 +21,7 @@ if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
   timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  step driver; timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 > $O/driver.json 2> $O/driver.err
+  step driver; timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 > $O/driver.json 2> $O/driver.err
   step 1000; timeout -k 10 200 $B > $O/coll.json 2> $O/coll.err
   step 8192; timeout -k 10 200 $B --agents-per-gpu 8192 > $O/8192.json 2> $O/8192.err
   step rank-share; timeout -k 10 200 $B --rank-share 8 --agents-total 8192 > $O/share.json 2> $O/share.err

@@ -38,7 +38,7 @@ run_one() {
     bench)
       while [ $# -ge 2 ]; do
         step bench "$1" "$2"
-        timeout -k 10 300 python3 bench.py $2 > "$O/$1.json" 2> "$O/$1.err"
+        timeout -k 10 300 python3 bench.py --full $2 > "$O/$1.json" 2> "$O/$1.err"
         shift 2
       done
       ;;
@@ -49,7 +49,7 @@ run_one() {
           local L=$la
           [ $v = b ] && L=$lb
           step ab $v $r
-          MPCCBF_LIB=$L timeout -k 10 200 python3 bench.py --no-cpu-baseline $args > "$O/${v}_$r.json" 2> "$O/${v}_$r.err"
+          MPCCBF_LIB=$L timeout -k 10 200 python3 bench.py --full --no-cpu-baseline $args > "$O/${v}_$r.json" 2> "$O/${v}_$r.err"
         done
       done
       ;;
@@ -57,7 +57,7 @@ run_one() {
       local name=$1 args=$2
       step prof "$name"
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$O/prof_$name" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline $args \
+        -d "$O/prof_$name" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline $args \
         > "$O/prof_$name.json" 2> "$O/prof_$name.err")
       ;;
     stamps)

@@ -15,7 +15,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 step() { echo "[$(date +%T)] $*"; }
 [ "$2" = "nopmc" ] || [ "$2" = "bench" ] || [ "$2" = "prof" ] || {
 pmc() {  # dir, bench args..., -- counters
@@ -24,7 +24,7 @@ pmc() {  # dir, bench args..., -- counters
   while [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
   step pmc $d "$@"
   timeout -s KILL 90 rocprofv3 --pmc "$@" --output-format csv -d $OUT/${TAG}_pmc/$d -o run \
-    -- python3 $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 "${args[@]}" > $OUT/${TAG}_pmc_$d.log 2>&1
+    -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "${args[@]}" > $OUT/${TAG}_pmc_$d.log 2>&1
 }
 SQA="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU"
 SQB="SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_LDS SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS"
@@ -69,7 +69,7 @@ step bench dense; timeout -k 10 300 $B --workload dense --steps 10 --warmup 2 > 
 prof() {  # name, bench args
   step prof $1
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_$1 -o run \
-    -- python3 $ROOT/bench.py --no-cpu-baseline ${@:2} > $OUT/${TAG}_prof_$1.json 2> $OUT/${TAG}_prof_$1.err
+    -- python3 $ROOT/bench.py --full --no-cpu-baseline ${@:2} > $OUT/${TAG}_prof_$1.json 2> $OUT/${TAG}_prof_$1.err
 }
 prof driver --steps 20 --warmup 5
 prof collision

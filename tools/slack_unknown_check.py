@@ -1,5 +1,5 @@
 """Oracle verdict on the non-OPTIMAL QPs of the all-neighbour slack stress line (diagnostics, CPU):
-reads a `bench.py --neighbours all --crowded --slack --dump f.npz` dump (statuses of the timed
+reads a `bench.py --full --neighbours all --crowded --slack --dump f.npz` dump (statuses of the timed
 steps and every step's state table), re-solves every agent-step whose IMPC statuses are not all
 OPTIMAL with the CPU oracle on the same states (every other robot as a neighbour), and prints
 both verdicts side by side.

@@ -1,4 +1,4 @@
-"""Why do a launch's slowest agents take many solver steps? Reads a `bench.py --dump` file written
+"""Why do a launch's slowest agents take many solver steps? Reads a `bench.py --full --dump` file written
 with the state trace (no --no-trace) and, for every agent of the timed steps whose IMPC iteration
 0 took at least MIN_STEPS solver steps, re-solves that QP with the oracle (CPU) and counts the
 sides active at its optimum (inequality rows within 1e-7 scaled of a bound): the dual active-set

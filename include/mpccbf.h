@@ -273,8 +273,13 @@ typedef struct mpccbf_run {
      * is that call's final table, unchanged since, with the same agent range and neighbour
      * query (knn_k, knn_radius). Its first step then reads the neighbour table the previous call's
      * last step filled, instead of rebuilding table 0 (two memsets and an insert launch per call).
-     * The library checks pointer, range and query against the previous call and rebuilds when any
-     * differs (or when an mpccbf_impc_solve in grid mode came between); 0: always rebuild. */
+     * That table holds copies of the states, so the rule is: only a grid-mode (nb_row_ptr NULL)
+     * mpccbf_run_steps call that ran at least one step leaves a rotation to continue. After any
+     * other call on the context (mpccbf_impc_solve in grid or CSR mode, mpccbf_run_steps with CSR
+     * lists, zero steps or zero agents) the next call rebuilds, and so does a call whose pointer,
+     * num_states, agent range or query differs from the previous call's. A caller that itself
+     * overwrites the final table between two grid-mode calls and still asks to continue is
+     * outside this contract (the library cannot see the write): pass 0. 0: always rebuild. */
     int32_t continue_tables;
 } mpccbf_run;
 

@@ -130,6 +130,9 @@ static int grid_tables(mpccbf_ctx* c, int num_states, uint32_t* (&cnt)[3], uint3
 int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                  int gstep = -1, unsigned long long* kclock = nullptr) {
     if (!c || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    // any step outside a grid-mode mpccbf_run_steps rotation (mpccbf_impc_solve, the CSR steps of
+    // mpccbf_run_steps) may write the state table a continuation would read: it must rebuild
+    if (gstep < 0) c->gcont.valid = false;
     if (b->num_agents < 0 || b->agent_first < 0 || b->agent_first + b->num_agents > b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent range outside states");
     if (b->num_agents == 0) return MPCCBF_OK;
@@ -155,8 +158,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         if (rc != MPCCBF_OK) return rc;
         const uint32_t T = grid_table_size(b->num_states);
         int rd = 0;
-        if (gstep < 0) {
-            c->gcont.valid = false;  // (table 0 rebuilt: a run_steps continuation must rebuild too)
+        if (gstep < 0) {  // (table 0 rebuilt here: gcont was cleared above)
             HIP_TRY(hipMemsetAsync(cnt[0], 0, (size_t)T * 4, stream));
             HIP_TRY(launch_grid_insert(b->states, b->num_states, 0, 0, b->knn_radius, cnt[0], slots[0], sst[0],
                                        stream));
@@ -723,6 +725,7 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
         // entry: that write follows this call's step barriers, or the abort below)
         if (!same) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: ranks of the in-process group differ in num_steps");
         if (r->num_steps == 0) {
+            c->gcont.valid = false;  // (as every call that does not end a grid rotation, see below)
             if (!lg->barrier()) return fail(MPCCBF_ERR_HIP, "run: a rank of the in-process group aborted");
             guard.g = nullptr;
             return MPCCBF_OK;
@@ -761,6 +764,11 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
     uint32_t *gcnt[3] = {}, *gslots[3] = {};
     double* gsst[3] = {};
     int gbase = 0;  // the first step's table index (gstep = gbase + s)
+    // Only a grid-mode call that ran at least one step leaves a rotation to continue. Every other
+    // call (CSR lists, zero steps, zero agents) clears the record: its steps, or the caller around
+    // a call that ran none, may have rewritten the recorded state table, whose states the
+    // neighbour table holds copies of.
+    if (!gtab) c->gcont.valid = false;
     if (gtab) {
         if (b->knn_k < 1 || !(b->knn_radius > 0))
             return fail(MPCCBF_ERR_INVALID_ARGUMENT, "grid neighbours need knn_k >= 1 and knn_radius > 0");

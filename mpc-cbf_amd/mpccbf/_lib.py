@@ -204,7 +204,8 @@ class PreparedRun:
         _check(self._fn(self._ctx._h, C.byref(self._b), C.byref(self._r), self._s))
         out = {"final": self._tables[0] if self._r.final_table == 0 else self._tables[1]}
         if self._solve_ms is not None:
-            out["step_ms"] = None if self._step_ms is None else self._step_ms[:self._n]
+            # copies: the library overwrites both host buffers at the next call
+            out["step_ms"] = None if self._step_ms is None else self._step_ms[:self._n].copy()
             sm = self._solve_ms[:self._n]
             out["solve_ms"] = sm[sm >= 0]
         return out

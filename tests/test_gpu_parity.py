@@ -319,7 +319,8 @@ def test_run_steps_continuation_matches_one_call(mpclib, first, count):
     """mpccbf_run::continue_tables (ABI 12): 3 + 4 + 5 steps in three calls, each continuing the
     previous call's neighbour-table rotation, == 12 steps in one call (bit-identical states and
     statuses); a continuation whose states are not the previous call's final table, or after an
-    mpccbf_impc_solve in grid mode, rebuilds the table and gives the same result."""
+    mpccbf_impc_solve in grid mode, rebuilds the table and gives the same result.
+    (Calls that rewrite the recorded table in place: test_gpu_context_reuse.py.)"""
     torch = _torch()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(512, seed=6)

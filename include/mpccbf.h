@@ -294,6 +294,50 @@ int mpccbf_set_variant(mpccbf_ctx* ctx, int variant);
 /* Name of the IMPC kernel instantiation the current variant launches (diagnostics). */
 const char* mpccbf_kernel_name(const mpccbf_ctx* ctx);
 
+/* Active-set store (feature macro; MPCCBF_ABI_VERSION is unchanged: no struct changed layout).
+ *
+ * Attach (store != NULL) or detach a caller-owned device buffer of rows x 8 int32, indexed by the
+ * agent's index into mpccbf_batch.states (rows >= num_states of every later call, else
+ * MPCCBF_ERR_INVALID_ARGUMENT at that call). Zero-filled = no record.
+ *
+ * Record of an agent, written by every mpccbf_impc_solve / mpccbf_run_steps step that solves it:
+ *   [0]     k, the number of sides of the final active set, 0 <= k <= 5
+ *   [1..5]  the sides' keys (k of them, the rest 0)
+ *   [6]     solver steps of the solve that produced the set, plus one per side that a warm start
+ *           offered that solve (so a set that was confirmed in 0 steps does not look worthless)
+ *   [7]     the IMPC iteration the set belongs to
+ * The set is the final active set of the iteration whose curve is returned in x (the last OPTIMAL
+ * iteration): the constraints that hold with equality there and carry a multiplier. The whole
+ * record is zero when no iteration was OPTIMAL, when the optimum came from a path without an exact
+ * active set (the interior-point solver), and for agents solved by a kernel without the store:
+ * slack mode, the FoV controller and the dense layouts (variants 1 / 3, non-separable operators)
+ * zero their agents' records and never read them. Supported: the separable collision controller
+ * without slack variables in both layouts (16 lanes per agent, one agent per wave) and their
+ * capacity launch; a record written by one layout is read by the other. While a store is attached
+ * mpccbf_options::lean is ignored (the 16-lane layout runs its full kernel).
+ *
+ * Keys do not depend on lanes, slots or the order of the neighbour list:
+ *   key >= 0, a box side:  key = (channel * 16 + row) * 2 + upper
+ *       channel 0 / 1 / 2 = x / y / yaw, upper = 1 for the row's upper bound, 0 for its lower;
+ *       row r of channel d is the r-th row, in order, among the rows of mpccbf_host_operators' G
+ *       whose non-zero columns are 2 d and 2 d + 1 (the separable layout: every row of G touches
+ *       one channel). The side is tight when G[i] y = hi[i] - Gs[i] s0 (upper; lo for lower).
+ *   key < 0, a CBF side:   key = -(1 + neighbour * 8 + sample)
+ *       neighbour = the other agent's index into mpccbf_batch.states, sample = the CBF sample k
+ *       (0 <= k < cbf_horizon <= 8) of the iteration's QP (iteration 0 has sample 0 only).
+ *
+ * With a store attached the dual active set warm-starts across steps: a solve reads the agent's
+ * record and, when [6] >= min_steps, maps its keys onto the new QP's own sides — box sides by
+ * (channel, row), every CBF side of neighbour j onto j's sample-0 row of iteration 0; keys whose
+ * neighbour left the list or whose row the filter dropped are skipped — and starts iteration 0
+ * from the equality QP on them if every multiplier has its side's sign, else cold. Statuses and
+ * solutions do not depend on the record (any subset of a QP's sides is a legal start and the
+ * optimum is unique); a stale or arbitrary record costs solver steps only. min_steps: 0 = the
+ * default (3), < 0 = export only, never warm-start. One buffer serves every step of
+ * mpccbf_run_steps, read and written in place; each rank touches its own agents' rows only. */
+#define MPCCBF_HAS_ACTIVE_STORE 1
+int mpccbf_set_active_store(mpccbf_ctx* ctx, int32_t* store, int32_t rows, int32_t min_steps);
+
 /* ABI 11: waves of the IMPC launch mpccbf_impc_solve / mpccbf_run_steps makes for num_agents
  * agents with the context's variant that write mpccbf_run::kernel_clock (0: that kernel has no
  * clock). */

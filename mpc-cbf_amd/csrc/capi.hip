@@ -25,14 +25,15 @@
 namespace mpccbf {
 
 hipError_t launch_impc(const DevOps& op, const double* buf, const ImpcArgs& a, int variant,
-                       hipStream_t s);
-const char* impc_kernel_name(const DevOps& op, int variant, int n);
+                       hipStream_t s, const StoreArgs& st);
+const char* impc_kernel_name(const DevOps& op, int variant, int n, bool store);
+bool impc_store_ok(const DevOps& op, int variant, int n);
 int impc_clock_waves(const DevOps& op, int variant, int n);
 hipError_t launch_impc_fov(const DevOps& op, const double* buf, const ImpcArgs& a, hipStream_t s);
 hipError_t launch_fov_rows_eval(int count, const double* ego, const double* nb, double fov, double Ds, double Rs,
                                 double bbx, double bby, double* vor, double* rows, hipStream_t s);
 hipError_t launch_impc_fallback(const DevOps& op, const double* buf, const ImpcArgs& a, bool wide,
-                                hipStream_t s);
+                                hipStream_t s, const StoreArgs& st);
 bool impc_may_defer(const DevOps& op, int variant, bool csr, int knn_k, int n);
 bool impc_rows_may_exceed(const DevOps& op, bool csr, int knn_k);
 int launch_neighbors(const double* states, int num_states, int first, int num_agents, int k,
@@ -81,6 +82,11 @@ struct mpccbf_ctx {
     int defer_parity = 0;
     int variant = 0;
     int last_n = 0;  // agents of the last IMPC launch (the kernel name depends on it: share-adaptive)
+    // active-set store (mpccbf_set_active_store): the caller's device buffer of store_rows records,
+    // or nullptr; store_min_steps as the kernels take it (>= 1, or < 0: export only)
+    int32_t* store = nullptr;
+    int store_rows = 0;
+    int store_min_steps = 0;
     // grid mode: where the previous mpccbf_run_steps call left the table rotation (ABI 12,
     // mpccbf_run::continue_tables): its final state table, shape, query and the next step's table
     struct {
@@ -92,6 +98,18 @@ struct mpccbf_ctx {
 };
 
 using namespace mpccbf;
+
+// The operators as the launches see them: while a store is attached the 16-lane layout runs its
+// full kernel (the lean main launch has no store instantiation; statuses and solutions are the
+// same, the lean launch only defers what it does not finish to the full pipeline)
+static DevOps launch_ops(const mpccbf_ctx* c) {
+    DevOps d = c->dev;
+    if (c->store) d.lean = 0;
+    return d;
+}
+
+// Warm-start threshold when mpccbf_set_active_store is given min_steps = 0
+constexpr int STORE_MIN_STEPS_DEFAULT = 3;
 
 static void pack(std::vector<double>& v, int32_t& off, const Mat& m) {
     off = (int32_t)v.size();
@@ -148,6 +166,10 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "traj_t (closed-loop fallback) needs the persistent x buffer");
     if (!(b->pos_std >= 0.0) || !(b->vel_std >= 0.0))
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "noise standard deviations must be >= 0");
+    if (c->store && c->store_rows < b->num_states)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows (" + std::to_string(c->store_rows) +
+                                                     ") < num_states (" + std::to_string(b->num_states) + ")");
+    const DevOps dops = launch_ops(c);
     ImpcArgs a;
     std::memset(&a, 0, sizeof(a));
     HIP_TRY(hipSetDevice(c->device));
@@ -209,7 +231,19 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     // fallback launch: agents the main launch defers (the lean launch: QPs that need the PDIP or
     // phase 1; beyond the separable kernel's 16 CBF row slots) are solved by a second launch of
     // the full separable pipeline (128 slots when the 16 can be exceeded)
-    const bool fb = c->dev.cbf_mode != 1 && impc_may_defer(c->dev, c->variant, !grid, b->knn_k, b->num_agents);
+    const bool fb = c->dev.cbf_mode != 1 && impc_may_defer(dops, c->variant, !grid, b->knn_k, b->num_agents);
+    // the store: read and written by the kernels that support it; any other launch leaves its
+    // agents' records zero (no record), so a record never outlives the solve it describes
+    StoreArgs st{nullptr, 0};
+    if (c->store) {
+        if (impc_store_ok(dops, c->variant, b->num_agents)) {
+            st.records = c->store;
+            st.min_steps = c->store_min_steps;
+        } else {
+            HIP_TRY(hipMemsetAsync(c->store + (size_t)b->agent_first * AS_WORDS, 0,
+                                   (size_t)b->num_agents * AS_WORDS * sizeof(int32_t), stream));
+        }
+    }
     c->last_n = b->num_agents;
     if (fb && c->defer_cap < b->num_agents) {
         if (c->defer) (void)hipFree(c->defer);
@@ -228,7 +262,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     a.defer = q_this;
     if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
     hipError_t e = c->dev.cbf_mode == 1 ? launch_impc_fov(c->dev, c->dbuf, a, stream)
-                                        : launch_impc(c->dev, c->dbuf, a, c->variant, stream);
+                                        : launch_impc(dops, c->dbuf, a, c->variant, stream, st);
     // the queues alternate only once the main launch is enqueued: a launch that failed zeroed no
     // header, so the next call must append to this step's queue again (zeroed by the launch before)
     if (e == hipSuccess && fb) c->defer_parity ^= 1;
@@ -238,7 +272,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         f.defer_clear = nullptr;
         f.kclock = nullptr;  // (the clock is the main launch's)
         f.queue = q_this;
-        e = launch_impc_fallback(c->dev, c->dbuf, f, impc_rows_may_exceed(c->dev, !grid, b->knn_k), stream);
+        e = launch_impc_fallback(dops, c->dbuf, f, impc_rows_may_exceed(dops, !grid, b->knn_k), stream, st);
         // (a queue the fallback never read is zeroed by the main launch after next)
     }
     if (e == hipSuccess && ev1) e = hipEventRecord(ev1, stream);
@@ -543,14 +577,25 @@ int mpccbf_impc_solve(mpccbf_ctx* c, const mpccbf_batch* b, void* stream) {
 }
 
 int32_t mpccbf_impc_launch_waves(const mpccbf_ctx* c, int32_t num_agents) {
-    return c ? impc_clock_waves(c->dev, c->variant, num_agents) : 0;
+    return c ? impc_clock_waves(launch_ops(c), c->variant, num_agents) : 0;
 }
 
 const char* mpccbf_kernel_name(const mpccbf_ctx* c) {
     if (!c) return "";
     if (c->dev.cbf_mode == 1) return c->dev.slack_mode ? "impc_fov_kernel<true>" : "impc_fov_kernel<false>";
-    const char* n = impc_kernel_name(c->dev, c->variant, c->last_n);
+    const char* n = impc_kernel_name(launch_ops(c), c->variant, c->last_n, c->store != nullptr);
     return n ? n : "";
+}
+
+int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t min_steps) {
+    if (rows < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows must be >= 0");
+    if (store != nullptr && rows == 0)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: a buffer needs rows >= 1");
+    if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null context");
+    c->store = store;
+    c->store_rows = store ? rows : 0;
+    c->store_min_steps = min_steps == 0 ? STORE_MIN_STEPS_DEFAULT : min_steps;
+    return MPCCBF_OK;
 }
 
 int mpccbf_set_variant(mpccbf_ctx* c, int variant) {
@@ -740,7 +785,7 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     const bool timing = r->step_ms || r->solve_ms;
-    const int kcw = impc_clock_waves(c->dev, c->variant, count);  // (pairs per step)
+    const int kcw = impc_clock_waves(launch_ops(c), c->variant, count);  // (pairs per step)
     if (r->kernel_clock && r->kernel_clock_waves < kcw)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: kernel_clock_waves < mpccbf_impc_launch_waves (" +
                                                      std::to_string(kcw) + ")");

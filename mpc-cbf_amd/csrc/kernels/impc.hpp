@@ -189,6 +189,20 @@ struct ImpcArgs {
     unsigned long long* kclock;
 };
 
+// active-set store (mpccbf_set_active_store), an argument of its own of the store kernels (not a
+// field of ImpcArgs: the kernels launched without a store keep their argument layout): num_states
+// x AS_WORDS int32 records; a record warm-starts iteration 0's solve when its steps word is >=
+// min_steps (< 0: never)
+struct StoreArgs {
+    int32_t* records;
+    int32_t min_steps;
+};
+
+// active-set store: int32 words per record, and the key of the CBF side (neighbour's state index,
+// CBF sample) — negative; box sides are (channel * 16 + row) * 2 + upper (active_store.hpp)
+constexpr int AS_WORDS = 8;
+__host__ __device__ inline int as_cbf_key(int nb, int sample) { return -(1 + nb * 8 + sample); }
+
 constexpr int NSTAMP = 8;
 
 }  // namespace mpccbf

@@ -592,6 +592,19 @@ __device__ __forceinline__ bool constant_rows_infeasible(const DevOps& op, const
     return grp_ballot<G>(bad) != 0ull;
 }
 
+// State index of list position j's neighbour (grid mode: the query's result in LDS; CSR: the
+// caller's list), for the active-set store's row keys
+__device__ __forceinline__ int nb_index(const ImpcArgs& args, bool grid_mode, const int32_t* idx, int nb0, int j) {
+    int v;
+    if (grid_mode) {
+        v = idx[j];
+    } else {
+        v = args.nb_col[nb0 + j];
+        asm volatile("" : "+v"(v));  // (the two reads kept apart: merged, one flat load)
+    }
+    return v;
+}
+
 // Ego state the CBF rows are evaluated at: s0 (iteration 0) or the previous curve at
 // h_samples(k) (iteration 1, ConnectivityIMPCCBF.cpp:161-168).
 template <int NZ>
@@ -618,11 +631,13 @@ __device__ __forceinline__ void cbf_ego_state(const DevOps& op, const double* bu
 // CBF rows of one IMPC iteration, filtered and compacted into `stage` ((NZ + 1) doubles per
 // row: coefficients then upper bound). Returns the group-uniform row count; *infeasible is set
 // when a single row already excludes every acceleration in the box.
-template <int NZ, int G>
+// TAG (the active-set store's instantiations): tags[slot] = the staged row's key, as_cbf_key
+// (neighbour's state index, sample); tags is LDS, written through an LDS-typed pointer.
+template <int NZ, int G, bool TAG = false>
 __device__ int stage_cbf_rows(const DevOps& op, const double* buf, const ImpcArgs& args, int it,
                               const double (&s0)[6], const double (&y)[NZ], bool grid_mode,
                               const NbScratch* nbs, int nb0, int nnb, double* stage, int cap, int gl,
-                              bool* infeasible) {
+                              bool* infeasible, int32_t* tags = nullptr) {
     const double* UZ = opp(buf, op.o_UZ);
     const double* US = opp(buf, op.o_US);
     const int nk = (it == 0) ? 1 : op.cbf_h;
@@ -687,6 +702,7 @@ __device__ int stage_cbf_rows(const DevOps& op, const double* buf, const ImpcArg
                 for (int jz = 0; jz < NZ; jz++)
                     dst[jz] = -(a[0] * UZk[jz] + a[1] * UZk[NZ + jz] + a[2] * UZk[2 * NZ + jz]);
                 dst[NZ] = b + (a[0] * us[0] + a[1] * us[1] + a[2] * us[2]);
+                if constexpr (TAG) lds_vol(tags)[slot] = as_cbf_key(nb_index(args, grid_mode, nbs->idx, nb0, j), k);
             }
             count += __popcll(msk);
         }
@@ -703,11 +719,11 @@ __device__ int stage_cbf_rows(const DevOps& op, const double* buf, const ImpcArg
 // time: lane 6 k + s the state, lane 18 + 3 k + d the U_k s0 term, 27 doubles) with the same
 // arithmetic as cbf_ego_state, and the pairs go in the same sample-major order: the staged rows
 // are bit-identical to stage_cbf_rows'.
-template <int NZ>
+template <int NZ, bool TAG = false>
 __device__ int stage_cbf_rows_pairs(const DevOps& op, const double* buf, const ImpcArgs& args, int it,
                                     const double (&s0)[6], const double (&y)[NZ], bool grid_mode,
                                     const NbScratch* nbs, int nb0, int nnb, double* stage, int cap, int gl,
-                                    bool* infeasible, double* smp) {
+                                    bool* infeasible, double* smp, int32_t* tags = nullptr) {
     constexpr int G = 16, KC = 3;
     const double* UZ = opp(buf, op.o_UZ);
     const double* US = opp(buf, op.o_US);
@@ -794,6 +810,7 @@ __device__ int stage_cbf_rows_pairs(const DevOps& op, const double* buf, const I
                 for (int jz = 0; jz < NZ; jz++)
                     dst[jz] = -(a[0] * UZk[jz] + a[1] * UZk[NZ + jz] + a[2] * UZk[2 * NZ + jz]);
                 dst[NZ] = b + (a[0] * smp[18 + 3 * kk] + a[1] * smp[18 + 3 * kk + 1] + a[2] * smp[18 + 3 * kk + 2]);
+                if constexpr (TAG) lds_vol(tags)[slot] = as_cbf_key(nb_index(args, grid_mode, nbs->idx, nb0, j), k0 + kk);
             }
             count += __popcll(msk);
         }

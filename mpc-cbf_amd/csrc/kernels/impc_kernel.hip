@@ -26,6 +26,7 @@
 #include "impc.hpp"
 #include "impc_common.hpp"
 #include "impc_wide.hpp"
+#include "active_store.hpp"
 #include "pdip.hpp"
 #include "pdip_sep.hpp"
 
@@ -479,16 +480,25 @@ __device__ __forceinline__ SepRows<SB, CB>& pick_rows(SepRows<SB, CB>& reg, SepR
 
 // (force-inlined: instantiated by two kernels, an out-of-line call would copy the kernel arguments
 // to the stack at every launch's start)
-template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false>
+// STORE (a store is attached, mpccbf_set_active_store; never in slack mode): the agent's record
+// starts iteration 0's solve and the returned curve's final active set is written back (astore:
+// this group's LDS for the staged CBF rows' keys; active_store.hpp).
+template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false, bool STORE = false>
 __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args,
                                const int ai, const int gl, double* stage, double* red, NbScratch& nbs,
-                               double* keep, SepRowsLds<SB, CB>* rows_lds = nullptr, double* bconst = nullptr) {
+                               double* keep, SepRowsLds<SB, CB>* rows_lds = nullptr, double* bconst = nullptr,
+                               int32_t* astore = nullptr, const StoreArgs store = StoreArgs{nullptr, 0}) {
+    static_assert(!(STORE && SLACK), "the active-set store is not built for slack mode");
     constexpr int G = 16;
     constexpr int NZ = SEP_NZ;
     constexpr int cap = CB * G;  // CBF rows per agent
     stamp(args, ai, gl, 0);
 
     const int self = args.agent_first + ai;
+    // (the record's load goes first: it has arrived when the state, issued after it, has)
+    int rec_in = 0;
+    if constexpr (STORE)
+        if (gl < AS_WORDS) rec_in = store.records[(size_t)self * AS_WORDS + gl];
     double s0[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) s0[i] = args.states[(size_t)self * 6 + i];
@@ -502,6 +512,14 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     // every load in flight, the query's included)
     asm volatile("" ::"v"(s0[0]), "v"(s0[1]), "v"(s0[2]), "v"(s0[3]), "v"(s0[4]), "v"(s0[5]));
     if (grid_mode) gq_begin<G>(args, s0[0], s0[1], gq);
+    // (LDS pointers by type, as lds_vol's other users: the accesses do not depend on inlining to be
+    // LDS accesses)
+    const lds_vptr<int32_t> tags = lds_vol(astore);
+    // (the record waits in the Newton sums' area, which only the interior-point solver uses, after
+    // iteration 0's start has been mapped: the main launch's LDS has no 32 bytes per group left)
+    const lds_vptr<int32_t> rec = lds_vol((int32_t*)red);
+    if constexpr (STORE)
+        if (gl < AS_WORDS) rec[gl] = rec_in;
     // the linear term and constant, group-uniform: kept in LDS (qk, after the warm-start ids) and
     // read back inside each IMPC iteration, so they are not live in registers across the loop
     double* qk = keep + 16 * (SEP_NZ + (LEAN ? 0 : 2 * SEP_D * SB)) + 8 + (SLACK ? 0 : POL_K + 1);
@@ -611,10 +629,31 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     double* act = s0k + 8;  // (no such area in slack mode: never touched there)
     if (!SLACK && gl == 0) act[POL_K] = 0.0;
     int steps0 = 0;  // iteration 0's solver steps
+    // STORE: the sides this iteration's solve was offered (iteration 0: the record's, mapped onto
+    // the staged rows), the staged row count, and this lane's word of the record to write
+    int k0_off = 0, cbf_count = 0, rec_out = 0;
     auto warm_count = [&](int it) -> int {
-        if (SLACK || it == 0 || op.das_warm <= 0 || steps0 < op.das_warm) return 0;
-        wave_lds_sync();
-        return (int)act[POL_K];
+        if constexpr (STORE) {
+            // iteration 1 carries iteration 0's set when that took das_warm steps, or when it was
+            // itself warm-started (then few steps say nothing) and ended with several sides.
+            // act[POL_K] < 0 afterwards: no solve of this iteration has saved a set
+            wave_lds_sync();
+            int k0 = 0;
+            if (it == 0) {
+                k0 = as_map_sep<CB>(rec, tags, cbf_count, op.sep_rows_per_dim, store.min_steps, gl, act);
+            } else if (op.das_warm > 0) {
+                const int kf = (int)act[POL_K];
+                if (kf > 0 && (steps0 >= op.das_warm || (k0_off > 0 && kf >= 2))) k0 = kf;
+            }
+            wave_lds_sync();
+            if (gl == 0) act[POL_K] = -1.0;
+            k0_off = k0;
+            return k0;
+        } else {
+            if (SLACK || it == 0 || op.das_warm <= 0 || steps0 < op.das_warm) return 0;
+            wave_lds_sync();
+            return (int)act[POL_K];
+        }
     };
 
     for (int it = 0; it < op.impc_iter; it++) {
@@ -651,12 +690,13 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             constexpr int STG = CB * 16 * (SEP_NZ + 1) > sep_pol_doubles<SB, CB>() ? CB * 16 * (SEP_NZ + 1)
                                                                                    : sep_pol_doubles<SB, CB>();
             if (STG - cap * (NZ + 1) >= 27 && it > 0)
-                count = stage_cbf_rows_pairs<NZ>(op, buf, args, it, sx, y, grid_mode, &nbs, nb0, nnb, stage, cap, gl,
-                                                 &row_infeasible, stage + cap * (NZ + 1));
+                count = stage_cbf_rows_pairs<NZ, STORE>(op, buf, args, it, sx, y, grid_mode, &nbs, nb0, nnb, stage, cap,
+                                                        gl, &row_infeasible, stage + cap * (NZ + 1), astore);
             else
-                count = stage_cbf_rows<NZ, G>(op, buf, args, it, sx, y, grid_mode, &nbs,
-                                              nb0, nnb, stage, cap, gl, &row_infeasible);
+                count = stage_cbf_rows<NZ, G, STORE>(op, buf, args, it, sx, y, grid_mode, &nbs,
+                                                     nb0, nnb, stage, cap, gl, &row_infeasible, astore);
             live = count > 0;
+            if constexpr (STORE) cbf_count = count;
 #pragma unroll
             for (int c = 0; c < CB; c++) {
                 const int ci = c * G + gl;
@@ -727,7 +767,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             const int k0 = warm_count(it);
             const int r = sep_dual_as<G, SB, CB>(rw, live, opp(buf, op.o_Pr), Pi, q, yu, op.tol, op.dual_as, stage, y,
                                                  prs, drs, nit, nullptr, true, tl, nullptr, k0, act,
-                                                 it == 0 ? act : nullptr, nullptr, bsc, bw);
+                                                 (STORE || it == 0) ? act : nullptr, nullptr, bsc, bw);
             if (r > 0) {
                 st = ST_OPTIMAL;
             } else if (r < 0 && tl > 10.0 * op.feas_tol) {
@@ -798,7 +838,8 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
                                                       ca, dbg, wslack, &vslack, red, &warm,
                                                       (attempt == 0 && warm_try) ? warm_delta : 0.0,
                                                       SLACK ? nullptr : stage, k0, SLACK ? nullptr : act,
-                                                      (!SLACK && attempt == 0 && it == 0) ? act : nullptr, bsc, bw);
+                                                      (!SLACK && attempt == 0 && (STORE || it == 0)) ? act : nullptr,
+                                                      bsc, bw);
                 total += po.iters;
                 ((attempt == 0 && warm_try) ? tr_warm : tr_cold) += po.iters;
                 if (po.status == ST_OPTIMAL) break;
@@ -884,6 +925,12 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
 #pragma unroll
             for (int i = 0; i < NZ; i++) ykeep[16 * i] = y[i];
             have_curve = true;
+            // the record of the curve kept so far: this solve's final set (steps: its own plus one
+            // per side a warm start offered, so that a set that converged at once stays eligible)
+            if constexpr (STORE) {
+                wave_lds_sync();
+                rec_out = as_word_sep(act, tags, nit + k0_off, it, gl);
+            }
         } else {
             success = false;
         }
@@ -900,6 +947,8 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     for (int i = 0; i < NZ; i++) yk[i] = ykeep[16 * i];
     load_state_lds(s0k, sx);
     write_agent_outputs<NZ, G>(op, buf, args, agent(), gl, sx, yk, have_curve, noise0);
+    if constexpr (STORE)
+        if (gl < AS_WORDS) store.records[(size_t)(args.agent_first + agent()) * AS_WORDS + gl] = rec_out;
     stamp(args, ai, gl, 7);
 }
 
@@ -951,6 +1000,41 @@ __global__ void __launch_bounds__(BS) impc_sep_kernel(const DevOps op, const dou
     }
 }
 
+// impc_sep_kernel (no slack mode, full pipeline) with the active-set store attached: a kernel of
+// its own with the store as a further argument, so that the kernels launched without a store are
+// the code they were — neither their body nor their argument layout knows of the store.
+template <int CB, int BS, bool QUEUE>
+__global__ void __launch_bounds__(BS) impc_sep_store_kernel(const DevOps op, const double* __restrict__ buf,
+                                                             const ImpcArgs args, const StoreArgs store) {
+    constexpr int SB = 1, GPB = BS / 16;
+    __shared__ double stage_all[GPB][sep_stage_doubles<SB, CB, false>()];
+    __shared__ double red_all[GPB][16 * (A_N + 1)];  // (also where the agent's record waits)
+    __shared__ NbScratch nb_scratch[GPB];
+    __shared__ double keep_all[GPB][sep_keep_doubles<SB, false, false>()];
+    __shared__ SepRowsLds<SB, CB> rows_lds[QUEUE ? BS : 1];
+    __shared__ double bconst_all[GPB][16 * 2 * SEP_D * SB + 8 * SEP_D * SB];
+    __shared__ int32_t tags_all[GPB][CB * 16];  // the staged CBF rows' keys
+    const int gl = threadIdx.x & 15;
+    const int gib = threadIdx.x / 16;
+    lds_poison();
+    if constexpr (!QUEUE) {
+        kclock_start(args);
+        grid_clear<BS>(args);
+        const int ai = xcd_block((int)blockIdx.x, (int)gridDim.x) * GPB + gib;
+        if (ai >= args.num_agents) return;
+        impc_sep_agent<SB, CB, false, false, false, true>(op, buf, args, ai, gl, stage_all[gib], red_all[gib],
+                                                          nb_scratch[gib], keep_all[gib], rows_lds, bconst_all[gib],
+                                                          tags_all[gib], store);
+        kclock_end<BS>(args);
+    } else {
+        const int k = blockIdx.x * GPB + gib;
+        if (k < args.queue[0])
+            impc_sep_agent<SB, CB, false, true, false, true>(op, buf, args, args.queue[2 + k], gl, stage_all[gib],
+                                                             red_all[gib], nb_scratch[gib], keep_all[gib],
+                                                             rows_lds + gib * 16, bconst_all[gib], tags_all[gib], store);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // One agent per wave (impc_wide.hpp)
 // ---------------------------------------------------------------------------------------------
@@ -961,12 +1045,20 @@ __device__ __forceinline__ void wide_defer(const ImpcArgs& args, int ai, int gl)
     }
 }
 
-__device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args,
-                                const int ai, WideLds& L) {
+// STORE: as impc_sep_agent's (astore: this wave's LDS, the staged CBF rows' keys then the record).
+template <bool STORE>
+__device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args, const int ai,
+                                WideLds& L, int32_t* astore = nullptr, const StoreArgs store = StoreArgs{nullptr, 0}) {
     constexpr int NZ = SEP_NZ;
     const int gl = (int)(threadIdx.x & 63u);
     stamp(args, ai, gl, 0);
     const int self = args.agent_first + ai;
+    // (the record's load goes first: it has arrived when the state, issued after it, has)
+    int rec_in = 0;
+    if constexpr (STORE)
+        if (gl < AS_WORDS) rec_in = store.records[(size_t)self * AS_WORDS + gl];
+    const lds_vptr<int32_t> tags = lds_vol(astore);
+    const lds_vptr<int32_t> rec = lds_vol(astore + (STORE ? W_CBF : 0));
     double s0[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) s0[i] = args.states[(size_t)self * 6 + i];
@@ -1009,6 +1101,8 @@ __device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf
         rw.su = rcp(1.0 + fabs(rw.hi));
     }
     wide_sample_us(op, buf, s0, L, gl);
+    if constexpr (STORE)
+        if (gl < AS_WORDS) rec[gl] = rec_in;
     if (grid_mode) wn_cells(args, gq, gc);
     const bool infeasible = constant_rows_infeasible<64>(op, buf, s0, gl);
     stamp(args, ai, gl, 1);
@@ -1059,6 +1153,7 @@ __device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf
     bool have_curve = false, success = true;
     if (gl == 0) L.act[POL_K] = 0.0;
     int steps0 = 0;
+    int k0_off = 0, rec_out = 0;  // STORE: the sides iteration 0 was offered; this lane's record word
     // per-iteration results, written together after the loop (impc_iter <= 2 here; more iterations
     // are written as they finish)
     int st_w0 = ST_UNKNOWN, st_w1 = ST_UNKNOWN, nit_w0 = 0, nit_w1 = 0;
@@ -1074,7 +1169,8 @@ __device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf
         }
         bool row_infeasible = false;
         long long* wd = it == 0 ? wdbg : nullptr;
-        const int count = uni_i(wide_cbf_rows(op, buf, args, it, s0, y, grid_mode, L, nb0, nnb, gl, row_infeasible, wd));
+        const int count =
+            uni_i(wide_cbf_rows<STORE>(op, buf, args, it, s0, y, grid_mode, L, nb0, nnb, gl, row_infeasible, wd, astore));
         bool nfin = false;
         if (gl >= W_BOX) {  // this iteration's CBF rows into the CBF lanes (unused: inert 0 <= 1)
             const int c = gl - W_BOX;
@@ -1110,13 +1206,26 @@ __device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf
             st = ST_INFEASIBLE;
         } else {
             int k0 = 0;
-            if (it > 0 && op.das_warm > 0 && steps0 >= op.das_warm) {
+            if constexpr (STORE) {
+                // (as impc_sep_agent's warm_count)
+                wave_lds_sync();
+                if (it == 0) {
+                    k0 = as_map_wide(rec, tags, count, op.sep_rows_per_dim, store.min_steps, gl, L.act);
+                } else if (op.das_warm > 0) {
+                    const int kf = (int)L.act[POL_K];
+                    if (kf > 0 && (steps0 >= op.das_warm || (k0_off > 0 && kf >= 2))) k0 = kf;
+                }
+                k0 = uni_i(k0);
+                wave_lds_sync();
+                if (gl == 0) L.act[POL_K] = -1.0;
+                k0_off = k0;
+            } else if (it > 0 && op.das_warm > 0 && steps0 >= op.das_warm) {
                 wave_lds_sync();
                 k0 = uni_i((int)L.act[POL_K]);
             }
             double tl = 0.0;
             const int r = wide_dual_as(rw, opp(buf, op.o_Pr), Pinv, q, yu, op.tol, op.dual_as, L.pol, y, prs, drs,
-                                       nit, tl, k0, L.act, it == 0 ? L.act : nullptr, want_rp, wd);
+                                       nit, tl, k0, L.act, (STORE || it == 0) ? L.act : nullptr, want_rp, wd);
             if (r > 0) {
                 st = ST_OPTIMAL;
                 if (!want_rp) prs = __builtin_nan("");
@@ -1150,6 +1259,10 @@ __device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf
 #pragma unroll
             for (int i = 0; i < NZ; i++) yk[i] = y[i];
             have_curve = true;
+            if constexpr (STORE) {
+                wave_lds_sync();
+                rec_out = as_word_wide(L.act, tags, nit + k0_off, it, gl);
+            }
         } else {
             success = false;
         }
@@ -1171,6 +1284,8 @@ __device__ void impc_wide_agent(const DevOps& op, const double* __restrict__ buf
     write_iteration(args, (size_t)ai * op.impc_iter, gl, st_w0, obj_w0, nit_w0, prs_w0, drs_w0);
     if (op.impc_iter > 1) write_iteration(args, (size_t)ai * op.impc_iter + 1, gl, st_w1, obj_w1, nit_w1, prs_w1, drs_w1);
     write_agent_outputs<NZ, 64>(op, buf, args, ai, gl, s0, yk, have_curve, L.noise);
+    if constexpr (STORE)
+        if (gl < AS_WORDS) store.records[(size_t)self * AS_WORDS + gl] = rec_out;
     stamp(args, ai, gl, 7);
 }
 
@@ -1207,11 +1322,73 @@ __global__ void __launch_bounds__(BS) WIDE_WPE_ATTR impc_wide_kernel(const DevOp
     const int wv = uni_i((int)(threadIdx.x >> 6));
     const int ai = xcd_block((int)blockIdx.x, (int)gridDim.x) * WPB + wv;
     if (ai >= args.num_agents) return;
-    impc_wide_agent(op, ops, args, ai, lds_all[wv]);
+    impc_wide_agent<false>(op, ops, args, ai, lds_all[wv]);
+    kclock_end<BS>(args);
+}
+
+// impc_wide_kernel with the active-set store attached (a kernel of its own, as impc_sep_store_kernel)
+template <int BS>
+__global__ void __launch_bounds__(BS) WIDE_WPE_ATTR impc_wide_store_kernel(const DevOps op,
+                                                                            const double* __restrict__ buf,
+                                                                            const ImpcArgs args, const StoreArgs store) {
+    constexpr int WPB = BS / 64;
+    constexpr int PER = WIDE_OPS / BS;
+    __shared__ WideLds lds_all[WPB];
+    __shared__ double ops[WIDE_OPS];
+    __shared__ int32_t astore_all[WPB][W_CBF + AS_WORDS];  // the staged CBF rows' keys, then the agent's record
+    lds_poison();
+    kclock_start(args);
+    {
+        double v[PER];
+#pragma unroll
+        for (int r = 0; r < PER; r++) {
+            const int i = r * BS + (int)threadIdx.x;
+            v[r] = i < op.hot ? buf[i] : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < PER; r++) ops[r * BS + threadIdx.x] = v[r];
+    }
+    grid_clear<BS>(args);
+    __syncthreads();
+    const int wv = uni_i((int)(threadIdx.x >> 6));
+    const int ai = xcd_block((int)blockIdx.x, (int)gridDim.x) * WPB + wv;
+    if (ai >= args.num_agents) return;
+    impc_wide_agent<true>(op, ops, args, ai, lds_all[wv], astore_all[wv], store);
     kclock_end<BS>(args);
 }
 
 }  // namespace dev
+
+// The store kernels are instantiated in a translation unit of their own (impc_store.hip, which
+// defines MPCCBF_STORE_TU and includes this file): compiled next to them, the kernels launched
+// without a store came out of the compiler with other operand orders and a few bytes longer
+// (DESIGN.md section 4). launch_impc_store: which = STORE_WIDE / STORE_SEP (main launches),
+// STORE_QUEUE1 / STORE_QUEUE8 (capacity launch with 1 / 8 CBF slots per lane).
+enum { STORE_WIDE = 0, STORE_SEP = 1, STORE_QUEUE1 = 2, STORE_QUEUE8 = 3 };
+hipError_t launch_impc_store(const DevOps& op, const double* buf, const ImpcArgs& a, const StoreArgs& st, int which,
+                             hipStream_t s);
+
+#ifdef MPCCBF_STORE_TU
+template <int CB, int BS, bool QUEUE>
+static hipError_t launch_impc_sep_store_t(const DevOps& op, const double* buf, const ImpcArgs& a, const StoreArgs& st,
+                                          hipStream_t s) {
+    constexpr int GPB = BS / 16;
+    const int blocks = (a.num_agents + GPB - 1) / GPB;
+    hipLaunchKernelGGL((dev::impc_sep_store_kernel<CB, BS, QUEUE>), dim3(blocks), dim3(BS), 0, s, op, buf, a, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_impc_store(const DevOps& op, const double* buf, const ImpcArgs& a, const StoreArgs& st, int which,
+                             hipStream_t s) {
+    if (which == STORE_SEP) return launch_impc_sep_store_t<1, 256, false>(op, buf, a, st, s);
+    if (which == STORE_QUEUE1) return launch_impc_sep_store_t<1, 64, true>(op, buf, a, st, s);
+    if (which == STORE_QUEUE8) return launch_impc_sep_store_t<8, 64, true>(op, buf, a, st, s);
+    constexpr int BS = 256, WPB = BS / 64;
+    const int blocks = (a.num_agents + WPB - 1) / WPB;
+    hipLaunchKernelGGL((dev::impc_wide_store_kernel<BS>), dim3(blocks), dim3(BS), 0, s, op, buf, a, st);
+    return hipGetLastError();
+}
+#else
 
 template <int NZ, int G, int R>
 static hipError_t launch_impc_t(const DevOps& op, const double* buf, const ImpcArgs& a,
@@ -1282,14 +1459,26 @@ static bool sep_lean(const DevOps& op, int variant, int n) {
 //   row slots when no agent can exceed them, else 8 slots per lane (128 rows). Agents beyond
 //   that report ERROR.
 hipError_t launch_impc_fallback(const DevOps& op, const double* buf, const ImpcArgs& a, bool wide,
-                                hipStream_t s) {
+                                hipStream_t s, const StoreArgs& st) {
     if (a.num_agents <= 0 || !a.queue) return hipSuccess;
     if (op.slack_mode) {
         if (slack_sb(op) == 2) return launch_impc_sep_t<2, 2, true, 64, true>(op, buf, a, s);
         return launch_impc_sep_t<1, 2, true, 64, true>(op, buf, a, s);
     }
+    // (a store is attached: the store instantiations, as the main launch's)
+    if (st.records != nullptr) return launch_impc_store(op, buf, a, st, wide ? STORE_QUEUE8 : STORE_QUEUE1, s);
     if (wide) return launch_impc_sep_t<1, 8, false, 64, true>(op, buf, a, s);
     return launch_impc_sep_t<1, 1, false, 64, true>(op, buf, a, s);
+}
+
+// Whether the launch for (operators, variant, agents) reads and writes the active-set store: the
+// separable collision controller without slack variables, 16-lane full kernel or wide kernel, and
+// their capacity launch. (The lean main launch has no store instantiation: the caller clears
+// DevOps::lean while a store is attached.)
+bool impc_store_ok(const DevOps& op, int variant, int n) {
+    if (op.cbf_mode != 0 || op.slack_mode || sep_lean(op, variant, n)) return false;
+    if (use_wide(op, variant, n)) return true;
+    return sep_variant(variant) && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16;
 }
 
 // Whether some agent can exceed the default separable kernel's 16 CBF row slots (caller lists,
@@ -1321,7 +1510,9 @@ int impc_clock_waves(const DevOps& op, int variant, int n) {
 }
 
 // Instantiation launch_impc picks for (operators, variant, agents per launch); nullptr if none fits.
-const char* impc_kernel_name(const DevOps& op, int variant, int n) {
+const char* impc_kernel_name(const DevOps& op, int variant, int n, bool store) {
+    if (store && impc_store_ok(op, variant, n))
+        return use_wide(op, variant, n) ? "impc_wide_store_kernel<256>" : "impc_sep_store_kernel<1,256,false>";
     if (op.slack_mode) {  // slack variables: separable layout, one lane per neighbour, cbf_h <= 2
         const int sb = slack_sb(op);
         return sb == 1 ? "impc_sep_kernel<1,2,true,256>" : (sb == 2 ? "impc_sep_kernel<2,2,true,128>" : nullptr);
@@ -1338,8 +1529,9 @@ const char* impc_kernel_name(const DevOps& op, int variant, int n) {
     return nullptr;
 }
 
+// st.records: set by the caller only where impc_store_ok
 hipError_t launch_impc(const DevOps& op, const double* buf, const ImpcArgs& a, int variant,
-                       hipStream_t s) {
+                       hipStream_t s, const StoreArgs& st) {
     if (a.num_agents <= 0) return hipSuccess;
     if (op.slack_mode) {
         const int sb = slack_sb(op);
@@ -1348,9 +1540,12 @@ hipError_t launch_impc(const DevOps& op, const double* buf, const ImpcArgs& a, i
         if (sb == 2) return launch_impc_sep_t<2, 2, true, 128>(op, buf, a, s);
         return hipErrorInvalidValue;
     }
-    if (use_wide(op, variant, a.num_agents)) return launch_impc_wide(op, buf, a, s);
+    const bool store = st.records != nullptr;
+    if (use_wide(op, variant, a.num_agents))
+        return store ? launch_impc_store(op, buf, a, st, STORE_WIDE, s) : launch_impc_wide(op, buf, a, s);
     if (sep_lean(op, variant, a.num_agents)) return launch_impc_sep_t<1, 1, false, 256, false, true>(op, buf, a, s);
     if (sep_variant(variant) && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16) {
+        if (store) return launch_impc_store(op, buf, a, st, STORE_SEP, s);
         return launch_impc_sep_t<1, 1, false>(op, buf, a, s);
     }
     if (op.nz == 6) {
@@ -1360,5 +1555,6 @@ hipError_t launch_impc(const DevOps& op, const double* buf, const ImpcArgs& a, i
     }
     return hipErrorInvalidValue;
 }
+#endif  // MPCCBF_STORE_TU
 
 }  // namespace mpccbf

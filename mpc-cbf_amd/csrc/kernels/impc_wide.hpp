@@ -687,9 +687,12 @@ __device__ __forceinline__ void wide_sample_us(const DevOps& op, const double* _
 // The CBF rows of IMPC iteration `it` (stage_cbf_rows on the wave: one (sample, neighbour) row per
 // lane, filtered and compacted into L.stage in (sample, neighbour) order). Returns the row count
 // (wave-uniform); row_infeasible: a row no acceleration in the box satisfies.
+// TAG (the active-set store's instantiation): tags[slot] = the staged row's key, as_cbf_key.
+template <bool TAG = false>
 __device__ int wide_cbf_rows(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args, int it,
                              const double (&s0)[6], const double (&y)[SEP_NZ], bool grid_mode, WideLds& L,
-                             int nb0, int nnb, int gl, bool& row_infeasible, long long* wdbg = nullptr) {
+                             int nb0, int nnb, int gl, bool& row_infeasible, long long* wdbg = nullptr,
+                             int32_t* tags = nullptr) {
     (void)wdbg;
     constexpr int NZ = SEP_NZ;
     WST(0);
@@ -773,6 +776,10 @@ __device__ int wide_cbf_rows(const DevOps& op, const double* __restrict__ buf, c
 #pragma unroll
             for (int jz = 0; jz < 4; jz++) dst[jz] = cg[jz];
             dst[4] = chi;
+            if constexpr (TAG) {
+                const int k = t / nnb, j = t - k * nnb;
+                lds_vol(tags)[slot] = as_cbf_key(nb_index(args, grid_mode, L.nbi, nb0, j), k);
+            }
         }
         count += __popcll(msk);
     }

@@ -23,7 +23,12 @@ EXPORTED = [
     "mpccbf_comm_create", "mpccbf_comm_destroy", "mpccbf_kernel_name", "mpccbf_fov_control_solve",
     "mpccbf_connectivity_control_solve", "mpccbf_host_operators", "mpccbf_host_last_error",
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
+    "mpccbf_set_active_store",
 ]
+
+# active-set store (mpccbf_set_active_store): int32 words per record, side keys per record
+ACTIVE_STORE_WORDS = 8
+ACTIVE_STORE_KEYS = 5
 
 
 class MpccbfError(RuntimeError):
@@ -40,6 +45,45 @@ def kernel_clock_us(clock) -> np.ndarray:
     start = np.where(on, t0, np.inf).min(axis=1)
     end = np.where(on, t1, -np.inf).max(axis=1)
     return np.where(np.isfinite(start), (end - start) * 1e-2, np.nan)
+
+
+def encode_active_side(side) -> int:
+    """Key of one active side: ("box", channel, row, side) with side 0 = lower / 1 = upper (or
+    "lower" / "upper"), or ("cbf", neighbour, sample). The encoding of include/mpccbf.h."""
+    if side[0] == "box":
+        _, channel, row, ul = side
+        ul = {"lower": 0, "upper": 1}.get(ul, ul)
+        if not (0 <= channel < 3 and 0 <= row < 16 and ul in (0, 1)):
+            raise ValueError(f"box side out of range: {side}")
+        return (channel * 16 + row) * 2 + ul
+    if side[0] == "cbf":
+        _, nb, sample = side
+        if not (nb >= 0 and 0 <= sample < 8):
+            raise ValueError(f"CBF side out of range: {side}")
+        return -(1 + nb * 8 + sample)
+    raise ValueError(f"unknown side kind: {side}")
+
+
+def decode_active_sides(record) -> list:
+    """The sides of one active-set record (8 int32: [k | keys | steps | iteration], see
+    mpccbf_set_active_store in include/mpccbf.h) as a list of ("box", channel, row, side) with
+    side 0 = lower / 1 = upper, and ("cbf", neighbour, sample)."""
+    rec = [int(v) for v in record]
+    if len(rec) != ACTIVE_STORE_WORDS:
+        raise ValueError(f"an active-set record has {ACTIVE_STORE_WORDS} words")
+    k = rec[0]
+    if not 0 <= k <= ACTIVE_STORE_KEYS:
+        raise ValueError(f"record holds k = {k} sides (0 .. {ACTIVE_STORE_KEYS})")
+    out = []
+    for key in rec[1:1 + k]:
+        if key >= 0:
+            if key >= 96:
+                raise ValueError(f"box key {key} out of range")
+            out.append(("box", key >> 5, (key >> 1) & 15, key & 1))
+        else:
+            v = -(key + 1)
+            out.append(("cbf", v >> 3, v & 7))
+    return out
 
 
 def status_name(s: int) -> str:
@@ -144,6 +188,8 @@ def load():
         getattr(L, f).argtypes = [vp]
     L.mpccbf_impc_solve.argtypes = [vp, C.POINTER(Batch), vp]
     L.mpccbf_set_variant.argtypes = [vp, C.c_int]
+    if hasattr(L, "mpccbf_set_active_store"):  # (MPCCBF_LIB may name a library from before the store)
+        L.mpccbf_set_active_store.argtypes = [vp, vp, C.c_int32, C.c_int32]
     L.mpccbf_build_neighbors.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_double, vp, vp, vp]
     L.mpccbf_qp_solve_dense.argtypes = [C.POINTER(DenseQP), vp, vp, vp]
@@ -238,6 +284,7 @@ class Context:
         self.impc_iter = int(cfg["impc_iter"])
         self.k_hor = int(cfg["k_hor"])
         self.device = device
+        self._active_store = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -252,6 +299,35 @@ class Context:
 
     def set_variant(self, v: int):
         _check(load().mpccbf_set_variant(self._h, v))
+
+    def set_active_store(self, store, min_steps: int = 0):
+        """Attach a (rows, 8) contiguous int32 device tensor as the active-set store, or detach
+        with None (mpccbf_set_active_store): every later solve writes each agent's final active
+        set into its row and warm-starts from it (min_steps: 0 = default threshold, < 0 = export
+        only). The context keeps a reference to the tensor while it is attached."""
+        if store is None:
+            _check(load().mpccbf_set_active_store(self._h, None, 0, int(min_steps)))
+            self._active_store = None
+            return
+        import torch
+        if not isinstance(store, torch.Tensor) or not store.is_cuda:
+            raise MpccbfError("the active store must be a device tensor")
+        if store.device.index != self.device:
+            raise MpccbfError(f"the active store is on {store.device}, the context on device {self.device}")
+        if store.dtype != torch.int32:
+            raise MpccbfError("the active store must be int32")
+        if store.dim() != 2 or store.shape[1] != ACTIVE_STORE_WORDS or store.shape[0] < 1:
+            raise MpccbfError(f"the active store must have shape (rows >= 1, {ACTIVE_STORE_WORDS})")
+        if not store.is_contiguous():
+            raise MpccbfError("the active store must be contiguous")
+        _check(load().mpccbf_set_active_store(self._h, store.data_ptr(), int(store.shape[0]), int(min_steps)))
+        self._active_store = store
+
+    def alloc_active_store(self, num_states: int, device=None):
+        """A zero-filled (num_states, 8) int32 store (no records) for set_active_store."""
+        import torch
+        dev = device or torch.device("cuda", self.device)
+        return torch.zeros((int(num_states), ACTIVE_STORE_WORDS), dtype=torch.int32, device=dev)
 
     @property
     def kernel_name(self) -> str:

@@ -54,11 +54,14 @@ class Simulator:
     """Closed-loop simulation of a swarm on one GPU, recording the example's states.json.
 
     neighbours: "knn" (the knn_k nearest within knn_radius, found on the device) or "all" (every
-    other robot, the reference's semantics, ConnectivityIMPCCBF.cpp:59-67)."""
+    other robot, the reference's semantics, ConnectivityIMPCCBF.cpp:59-67).
+    warm: attach an active-set store (Context.set_active_store), so every step starts each robot's
+    solve from its previous step's active set; self.active_store then holds the records of the
+    last step (mpccbf.decode_active_sides). Statuses and trajectories are those of warm=False."""
 
     def __init__(self, cfg: dict, states: np.ndarray, targets: np.ndarray, *, neighbours="knn",
                  knn_k=8, knn_radius=None, pos_std=0.0, vel_std=0.0, noise_seed=0, device=0,
-                 record=True, order="jacobi"):
+                 record=True, order="jacobi", warm=False):
         import torch
         if order not in ("jacobi", "gauss_seidel"):
             raise ValueError("order must be 'jacobi' or 'gauss_seidel'")
@@ -85,6 +88,10 @@ class Simulator:
                            nb_col=torch.tensor(col if len(col) else np.zeros(1, np.int32), device=self.dev))
         else:
             self.nb = dict(knn_k=knn_k, knn_radius=knn_radius or 3.0 * cfg["d_min"])
+        self.active_store = None
+        if warm:
+            self.active_store = self.ctx.alloc_active_store(n, device=self.dev)
+            self.ctx.set_active_store(self.active_store)
         self.gs_next = torch.empty((1, 6), dtype=torch.float64, device=self.dev)
         self.noise = dict(pos_std=pos_std, vel_std=vel_std, noise_seed=noise_seed)
         self.step_index = 0

@@ -170,7 +170,8 @@ int mpccbf_num_shared_rows(const mpccbf_ctx* ctx);
  *   nb_out      diagnostics, normally NULL (ABI 10): num_agents x 16 int32, the neighbour list each
  *               agent's QPs were built from, in the kernel's order (grid mode: the in-kernel query's
  *               k nearest, sorted by index; CSR: the given list), -1 after the last; lists longer
- *               than 16 are truncated here (not in the solve). */
+ *               than 16 are truncated here (not in the solve). Written by the release kernels of
+ *               every layout; in grid mode it is the list input of mpccbf_cap_audit_run. */
 typedef struct mpccbf_batch {
     int32_t num_states;
     const double* states;
@@ -337,6 +338,73 @@ const char* mpccbf_kernel_name(const mpccbf_ctx* ctx);
  * mpccbf_run_steps, read and written in place; each rank touches its own agents' rows only. */
 #define MPCCBF_HAS_ACTIVE_STORE 1
 int mpccbf_set_active_store(mpccbf_ctx* ctx, int32_t* store, int32_t rows, int32_t min_steps);
+
+/* Neighbour-cap audit (feature macro; MPCCBF_ABI_VERSION is unchanged: no struct changed layout).
+ *
+ * The reference hands every one of the N - 1 other robots to each robot's QP
+ * (ConnectivityIMPCCBF.cpp:59-67); a solve with capped lists (the knn_k nearest, or shorter CSR
+ * lists) drops rows. The QPs are strictly convex in the reduced variables, so a capped QP's optimum
+ * that satisfies every dropped row is also the unique optimum of the all-others QP, and a capped
+ * QP that is INFEASIBLE stays INFEASIBLE with more rows. mpccbf_cap_audit_run evaluates that
+ * certificate for a batch that mpccbf_impc_solve (or a one-step mpccbf_run_steps) just solved.
+ *
+ * batch: as the solve read and filled it — states the table that step read, the same agent_first,
+ * num_agents, targets / refs, knn_k / knn_radius; x and status as the solve wrote them (required).
+ * The lists are nb_row_ptr / nb_col (CSR mode; any order, duplicates allowed) or, in grid mode
+ * (nb_row_ptr NULL), the nb_out of that solve (required; knn_k <= 16, so it holds the whole list).
+ *
+ * Agent a's dropped set is every row j != a of states that is not in its list (no radius). A
+ * dropped row of IMPC iteration it and CBF sample k is the safety CBF row (a, b) of
+ * (ego e, state j): iteration 0 has sample 0 only, e = the agent's state; iteration 1 has
+ * k < cbf_horizon, e = position and velocity of the iteration-0 curve at parameter h k. The row is
+ * live when !(b >= bmax), bmax = sum_d max(-a_d a_min_d, -a_d a_max_d) (the solver's own exact drop
+ * rule, applied whatever mpccbf_options::no_cbf_filter says); a row with a non-finite b is not
+ * live. Its excess is v = -a . acc_it(h k) - b with acc_it the second derivative of iteration it's
+ * solution curve, its scaled excess v / (1 + |b|); it is violated when the scaled excess is above
+ * tol (0 = 1e-6, the solver's feasibility tolerance).
+ *
+ * counts[a] (8 int32):
+ *   [0]  live dropped rows of iteration 0
+ *   [1]  of those, violated by the iteration-0 solution (0 when status[0] is not OPTIMAL)
+ *   [2]  live dropped rows of iteration 1, over all samples
+ *   [3]  of those, violated by the iteration-1 solution (0 when status[1] is not OPTIMAL)
+ *   [4], [5]  the dropped neighbour (state index) with the largest scaled excess among the live
+ *        rows of iteration 0 / 1 (ties: the smaller index, then the smaller sample); -1 when there
+ *        is none or that iteration has no solution
+ *   [6]  size of the dropped set
+ *   [7]  certificate bits. Bit 0: iteration 0 is that of the all-others lists (status[0] OPTIMAL
+ *        and [1] == 0, or status[0] INFEASIBLE). Bit 1: iteration 1 likewise (bit 0, and status[1]
+ *        OPTIMAL with [3] == 0, or status[1] INFEASIBLE, or no iteration 1). Any other status
+ *        (ERROR, UNKNOWN after an attempted solve) sets no bit.
+ *   [2], [3], [5] are -1 when iteration 1 had no QP (impc_iter == 1, or status[0] not OPTIMAL).
+ * excess[a] = the largest scaled excess of iteration 0 and of iteration 1 (NaN where [4] / [5] is
+ * -1). live_nb[a] = the first 8 distinct dropped neighbours, in ascending state index, with a live
+ * row in either iteration, -1 padded. An agent whose own state or a listed neighbour's state is
+ * not finite audits as no live row and no bits.
+ *
+ * Iteration 0's solution is not returned by a solve whose iteration 1 succeeded, so the call runs
+ * the context's own IMPC launch once more on the batch with one iteration, into context scratch
+ * (no closed-loop state, no diagnostics, no active store read or written): the batch's x, status,
+ * obj, iters, traj_t and an attached store are left untouched. x0_out receives those iteration-0
+ * solutions (NaN where iteration 0 was not OPTIMAL). Like any mpccbf_impc_solve the call ends a
+ * mpccbf_run::continue_tables rotation (the next mpccbf_run_steps rebuilds its table; its results
+ * are those of a run without the audit). Asynchronous on the stream.
+ *
+ * Supported: the separable collision controller without slack variables in both layouts and their
+ * capacity launch (the audit itself does not depend on the layout), impc_iter <= 2; slack mode,
+ * the FoV controller and the dense layouts return MPCCBF_ERR_INVALID_ARGUMENT. Capacity: the
+ * kernel keeps one membership bitmap over states per agent in LDS, num_states <= 65,536
+ * (MPCCBF_ERR_CAPACITY beyond). Zero agents: MPCCBF_OK. */
+#define MPCCBF_HAS_CAP_AUDIT 1
+typedef struct mpccbf_cap_audit {
+    int32_t* counts;   /* out, num_agents x 8 */
+    double*  excess;   /* out, num_agents x 2, or NULL */
+    int32_t* live_nb;  /* out, num_agents x 8, or NULL */
+    double*  x0_out;   /* out, num_agents x n, or NULL: the iteration-0 solutions the audit used */
+    double   tol;      /* 0 = 1e-6 */
+} mpccbf_cap_audit;
+int mpccbf_cap_audit_run(mpccbf_ctx* ctx, const mpccbf_batch* batch, const mpccbf_cap_audit* audit,
+                         void* hip_stream);
 
 /* ABI 11: waves of the IMPC launch mpccbf_impc_solve / mpccbf_run_steps makes for num_agents
  * agents with the context's variant that write mpccbf_run::kernel_clock (0: that kernel has no

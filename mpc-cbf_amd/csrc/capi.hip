@@ -19,6 +19,7 @@
 #include "host/errors.hpp"
 #include "host/operators.hpp"
 #include "kernels/impc.hpp"
+#include "kernels/cap_audit.hpp"
 #include "kernels/cbf_control.hpp"
 #include "kernels/fov_cbf.hpp"
 
@@ -41,6 +42,7 @@ int launch_neighbors(const double* states, int num_states, int first, int num_ag
                      size_t scratch_bytes, hipStream_t s);
 size_t neighbors_scratch_bytes(int num_states, int num_agents, int k);
 size_t grid_table_bytes(int num_states);
+hipError_t launch_cap_audit(const DevOps& op, const double* buf, const AuditArgs& a, hipStream_t s);
 void grid_table_carve(void* base, int num_states, uint32_t** cnt, uint32_t** slots, double** sst);
 hipError_t launch_grid_insert(const double* states, int n, int skip0, int skip1, double radius,
                               uint32_t* cnt, uint32_t* slots, double* sst, hipStream_t s);
@@ -87,6 +89,11 @@ struct mpccbf_ctx {
     int32_t* store = nullptr;
     int store_rows = 0;
     int store_min_steps = 0;
+    // neighbour-cap audit (mpccbf_cap_audit_run): the second-derivative basis' offset in dbuf, and
+    // the scratch its iteration-0 launch writes (x0: agents x n doubles, then their statuses)
+    int32_t o_EB2 = 0;
+    void* audit_scratch = nullptr;
+    size_t audit_bytes = 0;
     // grid mode: where the previous mpccbf_run_steps call left the table rotation (ABI 12,
     // mpccbf_run::continue_tables): its final state table, shape, query and the next step's table
     struct {
@@ -502,6 +509,7 @@ int mpccbf_create(const mpccbf_params* p, const mpccbf_options* opt, mpccbf_ctx*
         pack(v, d.o_wvor, wv);
         pack(v, d.o_wfov, wf);
     }
+    pack(v, c->o_EB2, o.EB2);  // (after every operator of the solve kernels: their offsets stay)
     v.push_back(0.0);  // keep every offset addressable even for empty operators
     for (int i = 0; i < 3; i++) {
         d.a_lo[i] = o.a_lo[i];
@@ -565,6 +573,7 @@ void mpccbf_destroy(mpccbf_ctx* c) {
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->grid_scratch) (void)hipFree(c->grid_scratch);
     if (c->defer) (void)hipFree(c->defer);
+    if (c->audit_scratch) (void)hipFree(c->audit_scratch);
     delete c;
 }
 
@@ -595,6 +604,97 @@ int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t
     c->store = store;
     c->store_rows = store ? rows : 0;
     c->store_min_steps = min_steps == 0 ? STORE_MIN_STEPS_DEFAULT : min_steps;
+    return MPCCBF_OK;
+}
+
+int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_audit* au, void* stream_) {
+    // the checks that need no device first, then the context's
+    if (!b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: null batch");
+    if (!au) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: null audit");
+    if (!au->counts) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: counts is required");
+    if (!b->x || !b->status)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the solve's x and status are required");
+    const bool grid = b->nb_row_ptr == nullptr;
+    if (grid && !b->nb_out)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: grid mode needs the solve's nb_out");
+    if (b->num_agents < 0 || b->agent_first < 0 || b->agent_first + b->num_agents > b->num_states)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: agent range outside states");
+    if (!(au->tol >= 0.0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: tol must be >= 0");
+    if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null context");
+    if (c->dev.slack_mode) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: slack mode is not supported");
+    if (c->dev.cbf_mode == 1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the FoV controller is not supported");
+    {
+        DevOps full = c->dev;
+        full.lean = 0;
+        if (!impc_store_ok(full, c->variant, b->num_agents > 0 ? b->num_agents : 1))
+            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the separable layouts only (variants 0, 4, 5)");
+    }
+    if (c->p.impc_iter > 2) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: impc_iter > 2 is not supported");
+    if (b->num_agents == 0) return MPCCBF_OK;
+    if (!b->states || (!grid && !b->nb_col && b->num_states > 1))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: states / neighbour CSR missing");
+    if (b->num_states > AUDIT_MAX_STATES)
+        return fail(MPCCBF_ERR_CAPACITY, "cap audit: num_states (" + std::to_string(b->num_states) + ") > " +
+                                             std::to_string(AUDIT_MAX_STATES));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t xbytes = (size_t)b->num_agents * c->ops.n * sizeof(double);
+    const size_t need = xbytes + (size_t)b->num_agents * sizeof(int32_t);
+    if (need > c->audit_bytes) {
+        if (c->audit_scratch) (void)hipFree(c->audit_scratch);
+        c->audit_scratch = nullptr;
+        c->audit_bytes = 0;
+        HIP_TRY(hipMalloc(&c->audit_scratch, need));
+        c->audit_bytes = need;
+    }
+    double* x0 = (double*)c->audit_scratch;
+    int32_t* st0 = (int32_t*)((char*)c->audit_scratch + xbytes);
+    // iteration 0's solutions: the context's own IMPC launch once more on the same batch with one
+    // iteration, every output into scratch, no closed-loop state, no diagnostics, no active store
+    // (grid mode: gstep < 0 rebuilds the table from b->states, so the lists are the solve's)
+    {
+        mpccbf_batch sb = *b;
+        sb.x = x0;
+        sb.status = st0;
+        sb.obj = nullptr;
+        sb.iters = nullptr;
+        sb.next_states = nullptr;
+        sb.stamps = nullptr;
+        sb.traj_t = nullptr;
+        sb.pos_std = sb.vel_std = 0.0;
+        sb.primal_res = sb.dual_res = nullptr;
+        sb.substeps = nullptr;
+        sb.nb_out = nullptr;
+        const int32_t iters = c->dev.impc_iter;
+        int32_t* const store = c->store;
+        c->dev.impc_iter = 1;
+        c->store = nullptr;
+        const int rc = impc_enqueue(c, &sb, stream, nullptr, nullptr);
+        c->dev.impc_iter = iters;
+        c->store = store;
+        if (rc != MPCCBF_OK) return rc;
+    }
+    AuditArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.num_states = b->num_states;
+    a.states = b->states;
+    a.agent_first = b->agent_first;
+    a.num_agents = b->num_agents;
+    a.nb_row_ptr = b->nb_row_ptr;
+    a.nb_col = b->nb_col;
+    a.nb_list = grid ? b->nb_out : nullptr;
+    a.x = b->x;
+    a.status = b->status;
+    a.x0 = x0;
+    a.impc_iter = c->p.impc_iter;
+    a.o_EB2 = c->o_EB2;
+    a.h = c->p.h;
+    a.tol = au->tol > 0.0 ? au->tol : 1e-6;
+    a.counts = au->counts;
+    a.excess = au->excess;
+    a.live_nb = au->live_nb;
+    HIP_TRY(launch_cap_audit(c->dev, c->dbuf, a, stream));
+    if (au->x0_out) HIP_TRY(hipMemcpyAsync(au->x0_out, x0, xbytes, hipMemcpyDeviceToDevice, stream));
     return MPCCBF_OK;
 }
 

@@ -481,6 +481,7 @@ Operators build_operators(const mpccbf_params& p, bool keep_redundant) {
     }
     op.EB0 = bernstein_derivative_monomials(cv.C - 1, cv.T, 0);
     op.EB1 = bernstein_derivative_monomials(cv.C - 1, cv.T, 1);
+    op.EB2 = bernstein_derivative_monomials(cv.C - 1, cv.T, 2);
     op.cum = cv.cum;
     op.eval_step = p.Ts * (double)(int)(p.h / p.Ts);  // example :188-190, last sub-step
     if (p.cbf_mode == 1) {

@@ -48,6 +48,7 @@ struct Operators {
     Mat AZ, AS;               // (6 x nz), (6 x 6): state at t = h (closed-loop update)
     // closed-loop simulator (example :150-221): evaluate a stored curve at any t
     Mat EB0, EB1;             // C x C monomial coefficients of the Bernstein basis / derivative
+    Mat EB2;                  // likewise of the second derivative (the neighbour-cap audit's accelerations)
     std::vector<double> cum;  // cumulative piece parameters (SingleParameterPiecewiseCurve)
     double eval_step = 0.0;   // Ts * int(h / Ts): eval-time advance per control step
     // FoV controller (cbf_mode 1): Voronoi rows act on the piece-0 control points

@@ -23,12 +23,17 @@ EXPORTED = [
     "mpccbf_comm_create", "mpccbf_comm_destroy", "mpccbf_kernel_name", "mpccbf_fov_control_solve",
     "mpccbf_connectivity_control_solve", "mpccbf_host_operators", "mpccbf_host_last_error",
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
-    "mpccbf_set_active_store",
+    "mpccbf_set_active_store", "mpccbf_cap_audit_run",
 ]
 
 # active-set store (mpccbf_set_active_store): int32 words per record, side keys per record
 ACTIVE_STORE_WORDS = 8
 ACTIVE_STORE_KEYS = 5
+
+
+# neighbour-cap audit (mpccbf_cap_audit_run): int32 words per agent in counts, entries in live_nb
+CAP_AUDIT_WORDS = 8
+CAP_AUDIT_LIVE_NB = 8
 
 
 class MpccbfError(RuntimeError):
@@ -86,6 +91,23 @@ def decode_active_sides(record) -> list:
     return out
 
 
+def audit_summary(counts) -> dict:
+    """Totals of a neighbour-cap audit's counts (num_agents x 8 int32, mpccbf_cap_audit in
+    include/mpccbf.h; a tensor or an array; host-side): the live dropped rows and the violated ones
+    of IMPC iteration 0 / 1 (agents without an iteration 1, words -1, add nothing), the agents
+    whose iteration 0 / iteration 1 is certified to be that of the all-others lists (bits 0 / 1 of
+    word 7), and the agents without the full certificate."""
+    if hasattr(counts, "detach"):
+        counts = counts.detach().cpu().numpy()
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, CAP_AUDIT_WORDS)
+    tot = [int(np.clip(c[:, w], 0, None).sum()) for w in range(4)]
+    bit0 = int(np.count_nonzero(c[:, 7] & 1))
+    bit1 = int(np.count_nonzero(c[:, 7] & 2))
+    return {"agents": int(c.shape[0]), "live0": tot[0], "violated0": tot[1], "live1": tot[2],
+            "violated1": tot[3], "certified0": bit0, "certified1": bit1,
+            "uncertified": int(c.shape[0]) - bit1}
+
+
 def status_name(s: int) -> str:
     return STATUS_NAMES[s] if 0 <= s < len(STATUS_NAMES) else str(s)
 
@@ -140,6 +162,11 @@ class Batch(C.Structure):
     ]
 
 
+class CapAudit(C.Structure):
+    _fields_ = [("counts", C.c_void_p), ("excess", C.c_void_p), ("live_nb", C.c_void_p),
+                ("x0_out", C.c_void_p), ("tol", C.c_double)]
+
+
 class Run(C.Structure):
     _fields_ = [("num_steps", C.c_int32), ("states_alt", C.c_void_p), ("status_log", C.c_void_p),
                 ("iters_log", C.c_void_p), ("step_ms", C.c_void_p), ("solve_ms", C.c_void_p),
@@ -190,6 +217,8 @@ def load():
     L.mpccbf_set_variant.argtypes = [vp, C.c_int]
     if hasattr(L, "mpccbf_set_active_store"):  # (MPCCBF_LIB may name a library from before the store)
         L.mpccbf_set_active_store.argtypes = [vp, vp, C.c_int32, C.c_int32]
+    if hasattr(L, "mpccbf_cap_audit_run"):
+        L.mpccbf_cap_audit_run.argtypes = [vp, C.POINTER(Batch), C.POINTER(CapAudit), vp]
     L.mpccbf_build_neighbors.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_double, vp, vp, vp]
     L.mpccbf_qp_solve_dense.argtypes = [C.POINTER(DenseQP), vp, vp, vp]
@@ -285,6 +314,7 @@ class Context:
         self.k_hor = int(cfg["k_hor"])
         self.device = device
         self._active_store = None
+        self._last_knn = (0, 0.0)  # the neighbour query of the last solve (audit_neighbors' default)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -349,6 +379,7 @@ class Context:
         last successful curve and the next state follows it (see mpccbf_batch)."""
         if num_agents is None:
             num_agents = states.shape[0] - agent_first
+        self._last_knn = (int(knn_k), float(knn_radius))
         b = Batch(num_states=states.shape[0], states=_ptr(states), agent_first=agent_first,
                   num_agents=num_agents, targets=_ptr(targets), refs=_ptr(refs),
                   nb_row_ptr=_ptr(nb_row_ptr), nb_col=_ptr(nb_col), x=_ptr(x),
@@ -359,6 +390,40 @@ class Context:
                   cov=_ptr(cov), primal_res=_ptr(primal_res), dual_res=_ptr(dual_res),
                   substeps=_ptr(substeps), nb_out=_ptr(nb_out))
         _check(load().mpccbf_impc_solve(self._h, C.byref(b), _stream(stream)))
+
+    def audit_neighbors(self, states, *, x, status, targets=None, refs=None, nb_row_ptr=None, nb_col=None,
+                        nb_out=None, agent_first=0, num_agents=None, knn_k=None, knn_radius=None, tol=0.0,
+                        live_nb=False, x0=False, stream=None):
+        """Neighbour-cap audit of the batch impc_solve (or a one-step run_steps) just solved
+        (mpccbf_cap_audit_run): states, targets / refs, the agent range and knn_k / knn_radius as
+        in that solve (the query defaults to the context's last solve's), x and status as it filled them, and its lists: nb_row_ptr / nb_col, or in
+        grid mode the nb_out it wrote. Returns a dict of device tensors: counts (num_agents x 8
+        int32, see mpccbf_cap_audit; audit_summary() totals them), excess (num_agents x 2) and,
+        on request, live_nb (num_agents x 8 int32) and x0 (num_agents x n, the iteration-0
+        solutions). The solve's outputs and an attached active store are left untouched."""
+        import torch
+        if num_agents is None:
+            num_agents = states.shape[0] - agent_first
+        if knn_k is None:
+            knn_k = self._last_knn[0]
+        if knn_radius is None:
+            knn_radius = self._last_knn[1]
+        dev = states.device
+        rows = max(int(num_agents), 1)  # (at least one row: an empty tensor has no pointer to pass)
+        out = {"counts": torch.zeros((rows, CAP_AUDIT_WORDS), dtype=torch.int32, device=dev),
+               "excess": torch.full((rows, 2), float("nan"), dtype=torch.float64, device=dev)}
+        if live_nb:
+            out["live_nb"] = torch.full((rows, CAP_AUDIT_LIVE_NB), -1, dtype=torch.int32, device=dev)
+        if x0:
+            out["x0"] = torch.full((rows, self.n), float("nan"), dtype=torch.float64, device=dev)
+        b = Batch(num_states=states.shape[0], states=_ptr(states), agent_first=agent_first,
+                  num_agents=num_agents, targets=_ptr(targets), refs=_ptr(refs),
+                  nb_row_ptr=_ptr(nb_row_ptr), nb_col=_ptr(nb_col), x=_ptr(x), status=_ptr(status),
+                  knn_k=int(knn_k), knn_radius=float(knn_radius), nb_out=_ptr(nb_out))
+        a = CapAudit(counts=_ptr(out["counts"]), excess=_ptr(out["excess"]), live_nb=_ptr(out.get("live_nb")),
+                     x0_out=_ptr(out.get("x0")), tol=float(tol))
+        _check(load().mpccbf_cap_audit_run(self._h, C.byref(b), C.byref(a), _stream(stream)))
+        return {k: v[:max(int(num_agents), 0)] for k, v in out.items()}
 
     def run_steps(self, *args, **kw):
         """Closed-loop control steps on the device (mpccbf_run_steps): prepare_run_steps(...)()
@@ -382,6 +447,7 @@ class Context:
         stamps (as impc_solve; every step overwrites them)."""
         if num_agents is None:
             num_agents = states.shape[0] - agent_first
+        self._last_knn = (int(knn_k), float(knn_radius))
         if kernel_clock is not None:
             # the library writes num_steps x W x 2 uint64 words from the base pointer: a shorter,
             # narrower or strided tensor would be written out of bounds (W itself is checked

@@ -27,7 +27,7 @@ import math
 import numpy as np
 
 from . import swarm
-from ._lib import Context
+from ._lib import Context, audit_summary
 
 
 def bezier_positions(cfg: dict, x: np.ndarray, ts) -> np.ndarray:
@@ -57,14 +57,22 @@ class Simulator:
     other robot, the reference's semantics, ConnectivityIMPCCBF.cpp:59-67).
     warm: attach an active-set store (Context.set_active_store), so every step starts each robot's
     solve from its previous step's active set; self.active_store then holds the records of the
-    last step (mpccbf.decode_active_sides). Statuses and trajectories are those of warm=False."""
+    last step (mpccbf.decode_active_sides). Statuses and trajectories are those of warm=False.
+    audit: after every step, the neighbour-cap audit of that step's solve (Context.audit_neighbors):
+    self.audit_log gets one mpccbf.audit_summary per step, self.audit_counts / self.audit_excess hold
+    the last step's counts (device, n x 8) and largest scaled excesses (n x 2). Collision controller without slack variables, Jacobi order. Statuses,
+    trajectories and states_json() are those of audit=False."""
 
     def __init__(self, cfg: dict, states: np.ndarray, targets: np.ndarray, *, neighbours="knn",
                  knn_k=8, knn_radius=None, pos_std=0.0, vel_std=0.0, noise_seed=0, device=0,
-                 record=True, order="jacobi", warm=False):
+                 record=True, order="jacobi", warm=False, audit=False):
         import torch
         if order not in ("jacobi", "gauss_seidel"):
             raise ValueError("order must be 'jacobi' or 'gauss_seidel'")
+        if audit and order != "jacobi":
+            raise ValueError("audit=True needs order='jacobi'")
+        if audit and (cfg.get("cbf_mode", 0) == 1 or cfg.get("slack_mode", 0)):
+            raise ValueError("audit=True needs the collision controller without slack variables")
         self.order = order
         self.torch = torch
         self.cfg = dict(cfg)
@@ -92,6 +100,11 @@ class Simulator:
         if warm:
             self.active_store = self.ctx.alloc_active_store(n, device=self.dev)
             self.ctx.set_active_store(self.active_store)
+        self.audit = bool(audit)
+        self.audit_log = []
+        self.audit_counts = None
+        self.audit_excess = None
+        self.nb_out = torch.full((n, 16), -1, dtype=torch.int32, device=self.dev) if audit else None
         self.gs_next = torch.empty((1, 6), dtype=torch.float64, device=self.dev)
         self.noise = dict(pos_std=pos_std, vel_std=vel_std, noise_seed=noise_seed)
         self.step_index = 0
@@ -108,7 +121,15 @@ class Simulator:
         if self.order == "jacobi":
             self.ctx.impc_solve(self.states, targets=self.targets, x=o["x"], status=o["status"], obj=o["obj"],
                                 iters=o["iters"], next_states=self.next, traj_t=self.traj_t,
-                                substeps=self.substeps, step_index=self.step_index, **self.nb, **self.noise)
+                                substeps=self.substeps, step_index=self.step_index, nb_out=self.nb_out,
+                                **self.nb, **self.noise)
+            if self.audit:
+                # (self.states is the table the step read; the next states went to self.next)
+                lists = self.nb if self.csr else dict(nb_out=self.nb_out, **self.nb)
+                res = self.ctx.audit_neighbors(self.states, x=o["x"], status=o["status"], targets=self.targets,
+                                               **lists)
+                self.audit_counts, self.audit_excess = res["counts"], res["excess"]
+                self.audit_log.append(audit_summary(res["counts"]))
         else:
             # robot by robot (:140), each from the table as the robots before it left it (:201)
             self.next.copy_(self.states)  # (the states the robots re-plan from, for the record)

@@ -144,8 +144,13 @@ int mpccbf_num_shared_rows(const mpccbf_ctx* ctx);
  *               per IMPC iteration and agent (slack mode: 16 neighbours); an agent beyond it is
  *               re-solved in the same call by the fallback launch of the same separable solver
  *               with 8 CBF row slots per lane (128 rows; slack mode: the neighbours with a live
- *               row compacted into the 16 lanes); beyond that its QPs report ERROR. A QP whose
+ *               row compacted into the 16 lanes); beyond that its QPs report ERROR (the agent's
+ *               earlier iterations and every other agent are unaffected). A QP whose
  *               data is not finite (NaN / Inf state, target or neighbour state) reports ERROR
+ *               slack_mode requires cbf_horizon <= 2 (a neighbour's lane holds its rows of two
+ *               samples): with the collision controller a solve beyond it launches nothing and
+ *               returns MPCCBF_ERR_CAPACITY; with the FoV controller mpccbf_create refuses the
+ *               parameters (MPCCBF_ERR_INVALID_ARGUMENT)
  * Outputs (device, any may be NULL):
  *   x           num_agents x n: control points of the last OPTIMAL iteration (the curve the
  *               driver keeps, example :160-164); NaN if no iteration was OPTIMAL

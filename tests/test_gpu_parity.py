@@ -23,22 +23,25 @@ def _torch():
     return torch
 
 
-def run_gpu(ctx, states, targets, row_ptr, col, torch, cov=None):
+def run_gpu(ctx, states, targets, row_ptr, col, torch, cov=None, refs=None):
+    """refs (n x 3 k_hor): passed as mpccbf_batch.refs in place of the replicated targets."""
     dev = torch.device("cuda", 0)
     st = torch.tensor(states, dtype=torch.float64, device=dev)
-    tg = torch.tensor(targets, dtype=torch.float64, device=dev)
+    tg = None if refs is not None else torch.tensor(targets, dtype=torch.float64, device=dev)
+    rf = None if refs is None else torch.tensor(refs, dtype=torch.float64, device=dev)
     rp = torch.tensor(row_ptr, dtype=torch.int32, device=dev)
     cl = torch.tensor(col if len(col) else np.zeros(1, np.int32), dtype=torch.int32, device=dev)
     out = ctx.alloc_outputs(len(states))
     cv = None if cov is None else torch.tensor(cov, dtype=torch.float64, device=dev)
-    ctx.impc_solve(st, rp, cl, targets=tg, cov=cv, **out)
+    ctx.impc_solve(st, rp, cl, targets=tg, refs=rf, cov=cv, **out)
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def run_oracle(cfg, states, targets, row_ptr, col, agents, cov=None):
+def run_oracle(cfg, states, targets, row_ptr, col, agents, cov=None, refs=None):
     p = O.make_params(cfg)
-    refs = swarm.refs_from_targets(targets, cfg["k_hor"])
+    if refs is None:
+        refs = swarm.refs_from_targets(targets, cfg["k_hor"])
     res = []
     for a in agents:
         res.append(O.impc_optimize(p, states, a, col[row_ptr[a]:row_ptr[a + 1]], refs[a], covs=cov))

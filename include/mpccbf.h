@@ -411,6 +411,59 @@ typedef struct mpccbf_cap_audit {
 int mpccbf_cap_audit_run(mpccbf_ctx* ctx, const mpccbf_batch* batch, const mpccbf_cap_audit* audit,
                          void* hip_stream);
 
+/* Connectivity maintenance (feature macro; MPCCBF_ABI_VERSION is unchanged: no struct changed layout).
+ *
+ * Attach (c != NULL) or detach the connectivity rows of ConnectivityIMPCCBF
+ * (ConnectivityIMPCCBF.cpp:143-157, 177-192, which the reference keeps commented out;
+ * ConnectivityMPCCBFQPOperations.cpp:44-86, 111-173) to every later mpccbf_impc_solve /
+ * mpccbf_run_steps step of the context. A team is a contiguous range of rows of
+ * mpccbf_batch.states, team t = rows team_ptr[t] .. team_ptr[t+1]-1, 2 <= members <= 16; teams do
+ * not depend on the neighbour lists (the safety rows still come from the batch's CSR or k-nearest
+ * lists). Rows outside every team, and teams of one, get no new rows.
+ *
+ * Per step and team, from the table the step reads: the Laplacian weights
+ * w_ij = exp((d_max^2 - d_ij^2)^2 / sigma) - 1 for d_ij <= d_max (else 0), sigma = d_max^4 / ln 2
+ * (ConnectivityCBF::getLambda2), lambda2 and the unit Fiedler vector v (sign immaterial), by a
+ * launch of its own ahead of the step's IMPC launch on the same stream. lambda2 > lambda2_switch:
+ * the connectivity row, else the CLF rows. Rows of agent i per IMPC iteration: iteration 0 at sample
+ * k = 0 with the ego state e = the agent's state; iteration it > 0 at samples k < cbf_horizon with
+ * e = position and velocity of the previous iteration's curve at h k; the other members stay at
+ * their current states, lambda2 and v at their current-state values; U_k is the acceleration at
+ * sample k.
+ *   connectivity row:  -(g_x, g_y, 0)^T U_k x <= e_v^T H e_v + 5 g.e_v + 5 (g.e_v + 5 (lambda2 - lambda2_min)),
+ *       g / H the gradient / Hessian of lambda2 over the ego position with the Fiedler entries held
+ *       fixed, summed over every other member (ConnectivityCBF.cpp:430-512);
+ *   CLF rows, one per other member j:  +a^T U_k x <= -B,  V = (|p - p_j| - 2)^2, a = grad V,
+ *       B = Lf^2 V + 5 Lf V + 2 V (ConnectivityCBF.cpp:200-243; ConnectivityControl.cpp:72-82's sign).
+ * The safety rows' exact box-implication filter applies (mpccbf_options::no_cbf_filter keeps every
+ * row); a row that no acceleration satisfies makes the QP INFEASIBLE.
+ *
+ * While attached the solves run the connectivity launch (16 lanes per agent, 64 staged rows per
+ * agent and iteration: a full team of 16 at cbf_horizon 2 fits; beyond it the agent's QP reports
+ * ERROR) whatever mpccbf_set_variant says; mpccbf_kernel_name reports it. A team of more than 16
+ * members reports ERROR for its agents and NaN in lambda2; every other agent is unaffected. After a
+ * detach every call is what it was before the attach. An attached active-set store gets zero
+ * records from these launches; mpccbf_cap_audit_run returns MPCCBF_ERR_INVALID_ARGUMENT.
+ * team_ptr[num_teams] must not exceed num_states of a later solve (MPCCBF_ERR_INVALID_ARGUMENT at
+ * that call). With a communicator each rank computes the spectra of the teams that intersect its
+ * agent range (a team may straddle ranks: the state table is gathered).
+ *
+ * Refused with MPCCBF_ERR_INVALID_ARGUMENT: bad arguments (checked first, without a context),
+ * slack mode (the reference indexes the connectivity row's slack by self_idx into N - 1 slack
+ * variables), the FoV controller (cbf_mode 1), non-separable operators, d_max <= d_min. */
+#define MPCCBF_HAS_CONNECTIVITY 1
+typedef struct mpccbf_connectivity {
+    double d_max;
+    double lambda2_min;     /* 0 = 0.1 */
+    double lambda2_switch;  /* 0 = 0.1 */
+    int32_t num_teams;
+    const int32_t* team_ptr; /* HOST, num_teams + 1 non-decreasing offsets into the rows of `states`; copied */
+    double* lambda2;        /* out, device, num_teams, or NULL: this step's lambda2 per team (NaN: team > 16) */
+    double* fiedler;        /* out, device, team_ptr[num_teams] - team_ptr[0] entries (state row r at
+                               r - team_ptr[0]), or NULL */
+} mpccbf_connectivity;
+int mpccbf_set_connectivity(mpccbf_ctx* ctx, const mpccbf_connectivity* c /* NULL detaches */);
+
 /* ABI 11: waves of the IMPC launch mpccbf_impc_solve / mpccbf_run_steps makes for num_agents
  * agents with the context's variant that write mpccbf_run::kernel_clock (0: that kernel has no
  * clock). */

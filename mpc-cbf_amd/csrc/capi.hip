@@ -21,6 +21,7 @@
 #include "kernels/impc.hpp"
 #include "kernels/cap_audit.hpp"
 #include "kernels/cbf_control.hpp"
+#include "kernels/conn_rows.hpp"
 #include "kernels/fov_cbf.hpp"
 
 namespace mpccbf {
@@ -43,6 +44,11 @@ int launch_neighbors(const double* states, int num_states, int first, int num_ag
 size_t neighbors_scratch_bytes(int num_states, int num_agents, int k);
 size_t grid_table_bytes(int num_states);
 hipError_t launch_cap_audit(const DevOps& op, const double* buf, const AuditArgs& a, hipStream_t s);
+hipError_t launch_team_spectrum(const SpectrumArgs& a, hipStream_t s);
+hipError_t launch_impc_conn(const DevOps& op, const double* buf, const ImpcArgs& a, const ConnArgs& cn, hipStream_t s);
+bool impc_conn_ok(const DevOps& op);
+const char* impc_conn_kernel_name();
+int impc_conn_clock_waves(int n);
 void grid_table_carve(void* base, int num_states, uint32_t** cnt, uint32_t** slots, double** sst);
 hipError_t launch_grid_insert(const double* states, int n, int skip0, int skip1, double radius,
                               uint32_t* cnt, uint32_t* slots, double* sst, hipStream_t s);
@@ -96,6 +102,22 @@ struct mpccbf_ctx {
     size_t audit_bytes = 0;
     // grid mode: where the previous mpccbf_run_steps call left the table rotation (ABI 12,
     // mpccbf_run::continue_tables): its final state table, shape, query and the next step's table
+    // connectivity rows (mpccbf_set_connectivity): the teams (host copy), the caller's outputs, and
+    // the device tables the spectrum launch fills per step and the IMPC launch reads (ConnArgs;
+    // allocated at the first solve, rows: the state rows they cover)
+    struct {
+        bool on = false;
+        double dmax = 0.0, l2_min = 0.1, l2_switch = 0.1;
+        std::vector<int32_t> team_ptr;
+        double* out_l2 = nullptr;
+        double* out_fiedler = nullptr;
+        int rows = 0;
+        int32_t* d_team_ptr = nullptr;
+        int32_t* d_team_mode = nullptr;
+        int32_t* d_row_team = nullptr;
+        double* d_team_l2 = nullptr;
+        double* d_fiedler = nullptr;
+    } conn;
     struct {
         bool valid = false;
         const double* states = nullptr;
@@ -148,6 +170,43 @@ static int grid_tables(mpccbf_ctx* c, int num_states, uint32_t* (&cnt)[3], uint3
     return MPCCBF_OK;
 }
 
+static void conn_free(mpccbf_ctx* c) {
+    auto& k = c->conn;
+    if (k.d_team_ptr) (void)hipFree(k.d_team_ptr);
+    if (k.d_team_mode) (void)hipFree(k.d_team_mode);
+    if (k.d_row_team) (void)hipFree(k.d_row_team);
+    if (k.d_team_l2) (void)hipFree(k.d_team_l2);
+    if (k.d_fiedler) (void)hipFree(k.d_fiedler);
+    k.d_team_ptr = k.d_team_mode = k.d_row_team = nullptr;
+    k.d_team_l2 = k.d_fiedler = nullptr;
+    k.rows = 0;
+}
+
+// The connectivity tables for a state table of num_states rows (grown on demand; the team offsets
+// and the rows' teams are uploaded here, the rest is written by every step's spectrum launch).
+static int conn_tables(mpccbf_ctx* c, int num_states) {
+    auto& k = c->conn;
+    if (k.d_team_ptr && k.rows >= num_states) return MPCCBF_OK;
+    conn_free(c);
+    const size_t nt = k.team_ptr.size() - 1, rows = (size_t)std::max(num_states, 1);
+    HIP_TRY(hipMalloc(&k.d_team_ptr, (nt + 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&k.d_team_mode, std::max<size_t>(nt, 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&k.d_team_l2, std::max<size_t>(nt, 1) * sizeof(double)));
+    HIP_TRY(hipMalloc(&k.d_row_team, rows * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&k.d_fiedler, rows * sizeof(double)));
+    std::vector<int32_t> row_team(rows, -1);
+    for (size_t t = 0; t < nt; t++)
+        if (k.team_ptr[t + 1] - k.team_ptr[t] >= 2)  // (teams of one: no rows)
+            for (int32_t r = k.team_ptr[t]; r < k.team_ptr[t + 1] && r < num_states; r++) row_team[r] = (int32_t)t;
+    HIP_TRY(hipMemcpy(k.d_team_ptr, k.team_ptr.data(), (nt + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.d_row_team, row_team.data(), rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(k.d_team_mode, 0, std::max<size_t>(nt, 1) * sizeof(int32_t)));
+    HIP_TRY(hipMemset(k.d_team_l2, 0, std::max<size_t>(nt, 1) * sizeof(double)));
+    HIP_TRY(hipMemset(k.d_fiedler, 0, rows * sizeof(double)));
+    k.rows = (int)rows;
+    return MPCCBF_OK;
+}
+
 // One IMPC step for a batch, enqueued on `stream`; ev0 / ev1 (optional) are recorded around the
 // IMPC kernel alone. Grid mode: gstep < 0 builds table 0 from b->states first (memset + insert
 // kernel); gstep >= 0 (mpccbf_run_steps) reads table gstep % 3, which the previous step filled,
@@ -176,10 +235,45 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     if (c->store && c->store_rows < b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows (" + std::to_string(c->store_rows) +
                                                      ") < num_states (" + std::to_string(b->num_states) + ")");
+    const bool conn = c->conn.on;
+    if (conn && c->conn.team_ptr.back() > b->num_states)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr ends at row " +
+                                                     std::to_string(c->conn.team_ptr.back()) + " > num_states (" +
+                                                     std::to_string(b->num_states) + ")");
     const DevOps dops = launch_ops(c);
     ImpcArgs a;
     std::memset(&a, 0, sizeof(a));
     HIP_TRY(hipSetDevice(c->device));
+    ConnArgs cn;
+    std::memset(&cn, 0, sizeof(cn));
+    if (conn) {
+        // this step's spectra, ahead of the IMPC launch on the same stream, from the table it reads
+        const int rc = conn_tables(c, b->num_states);
+        if (rc != MPCCBF_OK) return rc;
+        const auto& k = c->conn;
+        SpectrumArgs sp;
+        std::memset(&sp, 0, sizeof(sp));
+        sp.num_teams = (int32_t)k.team_ptr.size() - 1;
+        sp.team_ptr = k.d_team_ptr;
+        sp.states = b->states;
+        sp.first = b->agent_first;
+        sp.count = b->num_agents;
+        sp.dmax = k.dmax;
+        sp.l2_switch = k.l2_switch;
+        sp.team_l2 = k.d_team_l2;
+        sp.team_mode = k.d_team_mode;
+        sp.fiedler = k.d_fiedler;
+        sp.out_l2 = k.out_l2;
+        sp.out_fiedler = k.out_fiedler;
+        HIP_TRY(launch_team_spectrum(sp, stream));
+        cn.row_team = k.d_row_team;
+        cn.team_ptr = k.d_team_ptr;
+        cn.team_mode = k.d_team_mode;
+        cn.team_l2 = k.d_team_l2;
+        cn.fiedler = k.d_fiedler;
+        cn.dmax = k.dmax;
+        cn.l2_min = k.l2_min;
+    }
     if (grid) {
         uint32_t *cnt[3], *slots[3];
         double* sst[3];
@@ -238,12 +332,13 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     // fallback launch: agents the main launch defers (the lean launch: QPs that need the PDIP or
     // phase 1; beyond the separable kernel's 16 CBF row slots) are solved by a second launch of
     // the full separable pipeline (128 slots when the 16 can be exceeded)
-    const bool fb = c->dev.cbf_mode != 1 && impc_may_defer(dops, c->variant, !grid, b->knn_k, b->num_agents);
+    // (the connectivity launch has no capacity launch behind it: beyond its rows, ERROR)
+    const bool fb = !conn && c->dev.cbf_mode != 1 && impc_may_defer(dops, c->variant, !grid, b->knn_k, b->num_agents);
     // the store: read and written by the kernels that support it; any other launch leaves its
     // agents' records zero (no record), so a record never outlives the solve it describes
     StoreArgs st{nullptr, 0};
     if (c->store) {
-        if (impc_store_ok(dops, c->variant, b->num_agents)) {
+        if (!conn && impc_store_ok(dops, c->variant, b->num_agents)) {
             st.records = c->store;
             st.min_steps = c->store_min_steps;
         } else {
@@ -268,8 +363,9 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     }
     a.defer = q_this;
     if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
-    hipError_t e = c->dev.cbf_mode == 1 ? launch_impc_fov(c->dev, c->dbuf, a, stream)
-                                        : launch_impc(dops, c->dbuf, a, c->variant, stream, st);
+    hipError_t e = conn ? launch_impc_conn(dops, c->dbuf, a, cn, stream)
+                        : (c->dev.cbf_mode == 1 ? launch_impc_fov(c->dev, c->dbuf, a, stream)
+                                                : launch_impc(dops, c->dbuf, a, c->variant, stream, st));
     // the queues alternate only once the main launch is enqueued: a launch that failed zeroed no
     // header, so the next call must append to this step's queue again (zeroed by the launch before)
     if (e == hipSuccess && fb) c->defer_parity ^= 1;
@@ -574,6 +670,7 @@ void mpccbf_destroy(mpccbf_ctx* c) {
     if (c->grid_scratch) (void)hipFree(c->grid_scratch);
     if (c->defer) (void)hipFree(c->defer);
     if (c->audit_scratch) (void)hipFree(c->audit_scratch);
+    conn_free(c);
     delete c;
 }
 
@@ -586,11 +683,14 @@ int mpccbf_impc_solve(mpccbf_ctx* c, const mpccbf_batch* b, void* stream) {
 }
 
 int32_t mpccbf_impc_launch_waves(const mpccbf_ctx* c, int32_t num_agents) {
-    return c ? impc_clock_waves(launch_ops(c), c->variant, num_agents) : 0;
+    if (!c) return 0;
+    if (c->conn.on) return impc_conn_clock_waves(num_agents);
+    return impc_clock_waves(launch_ops(c), c->variant, num_agents);
 }
 
 const char* mpccbf_kernel_name(const mpccbf_ctx* c) {
     if (!c) return "";
+    if (c->conn.on) return impc_conn_kernel_name();
     if (c->dev.cbf_mode == 1) return c->dev.slack_mode ? "impc_fov_kernel<true>" : "impc_fov_kernel<false>";
     const char* n = impc_kernel_name(launch_ops(c), c->variant, c->last_n, c->store != nullptr);
     return n ? n : "";
@@ -604,6 +704,49 @@ int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t
     c->store = store;
     c->store_rows = store ? rows : 0;
     c->store_min_steps = min_steps == 0 ? STORE_MIN_STEPS_DEFAULT : min_steps;
+    return MPCCBF_OK;
+}
+
+int mpccbf_set_connectivity(mpccbf_ctx* c, const mpccbf_connectivity* k) {
+    // the checks that need no context first, then the context's
+    if (k) {
+        if (!(k->d_max > 0.0) || !std::isfinite(k->d_max))
+            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: d_max must be positive and finite");
+        if (!(k->lambda2_min >= 0.0) || !std::isfinite(k->lambda2_min) || !(k->lambda2_switch >= 0.0) ||
+            !std::isfinite(k->lambda2_switch))
+            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: lambda2_min and lambda2_switch must be >= 0 and finite");
+        if (k->num_teams < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: num_teams < 0");
+        if (!k->team_ptr) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr is required");
+        if (k->team_ptr[0] < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr[0] < 0");
+        for (int32_t t = 0; t < k->num_teams; t++)
+            if (k->team_ptr[t + 1] < k->team_ptr[t])
+                return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr decreases at team " + std::to_string(t));
+    }
+    if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null context");
+    if (!k) {
+        // (the device tables are freed: kernels in flight finish first, hipFree waits for the device)
+        (void)hipSetDevice(c->device);
+        conn_free(c);
+        c->conn.on = false;
+        c->conn.team_ptr.clear();
+        c->conn.out_l2 = c->conn.out_fiedler = nullptr;
+        return MPCCBF_OK;
+    }
+    if (c->dev.slack_mode) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: slack mode is not supported");
+    if (c->dev.cbf_mode == 1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: the FoV controller is not supported");
+    if (!(k->d_max > c->p.d_min)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: d_max must exceed d_min");
+    if (!impc_conn_ok(c->dev))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: the separable collision controller only");
+    (void)hipSetDevice(c->device);
+    conn_free(c);
+    auto& d = c->conn;
+    d.on = true;
+    d.dmax = k->d_max;
+    d.l2_min = k->lambda2_min == 0.0 ? 0.1 : k->lambda2_min;
+    d.l2_switch = k->lambda2_switch == 0.0 ? 0.1 : k->lambda2_switch;
+    d.team_ptr.assign(k->team_ptr, k->team_ptr + k->num_teams + 1);
+    d.out_l2 = k->lambda2;
+    d.out_fiedler = k->fiedler;
     return MPCCBF_OK;
 }
 
@@ -621,6 +764,8 @@ int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: agent range outside states");
     if (!(au->tol >= 0.0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: tol must be >= 0");
     if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null context");
+    if (c->conn.on)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: not supported while connectivity is attached");
     if (c->dev.slack_mode) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: slack mode is not supported");
     if (c->dev.cbf_mode == 1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the FoV controller is not supported");
     {
@@ -885,7 +1030,7 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     const bool timing = r->step_ms || r->solve_ms;
-    const int kcw = impc_clock_waves(launch_ops(c), c->variant, count);  // (pairs per step)
+    const int kcw = mpccbf_impc_launch_waves(c, count);  // (pairs per step)
     if (r->kernel_clock && r->kernel_clock_waves < kcw)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: kernel_clock_waves < mpccbf_impc_launch_waves (" +
                                                      std::to_string(kcw) + ")");

@@ -29,6 +29,7 @@
 #include "active_store.hpp"
 #include "pdip.hpp"
 #include "pdip_sep.hpp"
+#include "conn_rows.hpp"
 
 namespace mpccbf {
 namespace dev {
@@ -483,12 +484,17 @@ __device__ __forceinline__ SepRows<SB, CB>& pick_rows(SepRows<SB, CB>& reg, SepR
 // STORE (a store is attached, mpccbf_set_active_store; never in slack mode): the agent's record
 // starts iteration 0's solve and the returned curve's final active set is written back (astore:
 // this group's LDS for the staged CBF rows' keys; active_store.hpp).
-template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false, bool STORE = false>
+// CONN (connectivity attached, mpccbf_set_connectivity; impc_conn.hip alone instantiates it): the
+// team's connectivity rows are staged behind the safety rows of every iteration (conn_rows.hpp);
+// rows in LDS as the capacity launch keeps them.
+template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false, bool STORE = false, bool CONN = false>
 __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args,
                                const int ai, const int gl, double* stage, double* red, NbScratch& nbs,
                                double* keep, SepRowsLds<SB, CB>* rows_lds = nullptr, double* bconst = nullptr,
-                               int32_t* astore = nullptr, const StoreArgs store = StoreArgs{nullptr, 0}) {
+                               int32_t* astore = nullptr, const StoreArgs store = StoreArgs{nullptr, 0},
+                               const ConnArgs conn = ConnArgs{}) {
     static_assert(!(STORE && SLACK), "the active-set store is not built for slack mode");
+    static_assert(!CONN || (!SLACK && !STORE && !LEAN), "connectivity rows: the full non-slack pipeline");
     constexpr int G = 16;
     constexpr int NZ = SEP_NZ;
     constexpr int cap = CB * G;  // CBF rows per agent
@@ -547,7 +553,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     if (grid_mode) gq_slots<G>(args, gq, gl);
     SepRows<SB, CB> rw_reg;  // (the fallback launch: rows in LDS)
     // (rows in LDS: the fallback launch, and two box slots per lane, where in registers they spill)
-    SepRows<SB, CB>& rw = pick_rows<QUEUE || (SB > 1)>(rw_reg, rows_lds);
+    SepRows<SB, CB>& rw = pick_rows<QUEUE || CONN || (SB > 1)>(rw_reg, rows_lds);
     {
         const double* B = opp(buf, op.o_Gsep);
 #pragma unroll
@@ -695,6 +701,11 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             else
                 count = stage_cbf_rows<NZ, G, STORE>(op, buf, args, it, sx, y, grid_mode, &nbs,
                                                      nb0, nnb, stage, cap, gl, &row_infeasible, astore);
+#ifdef MPCCBF_CONN_TU
+            if constexpr (CONN)
+                count = stage_conn_rows<NZ>(op, buf, args, conn, args.agent_first + agent(), it, sx, y,
+                                            stage, cap, count, gl, &row_infeasible);
+#endif
             live = count > 0;
             if constexpr (STORE) cbf_count = count;
 #pragma unroll
@@ -1034,6 +1045,35 @@ __global__ void __launch_bounds__(BS) impc_sep_store_kernel(const DevOps op, con
                                                              rows_lds + gib * 16, bconst_all[gib], tags_all[gib], store);
     }
 }
+
+#ifdef MPCCBF_CONN_TU
+// impc_sep_kernel (no slack mode, full pipeline) with connectivity attached: a kernel of its own
+// with the connectivity tables as a further argument (as impc_sep_store_kernel). One agent per
+// 16-lane group, CB CBF row slots per lane with the rows in LDS; an agent beyond CB * 16 staged
+// rows reports ERROR (no capacity launch behind it).
+template <int CB, int BS>
+__global__ void __launch_bounds__(BS) impc_sep_conn_kernel(const DevOps op, const double* __restrict__ buf,
+                                                            const ImpcArgs args, const ConnArgs conn) {
+    constexpr int SB = 1, GPB = BS / 16;
+    __shared__ double stage_all[GPB][sep_stage_doubles<SB, CB, false>()];
+    __shared__ double red_all[GPB][16 * (A_N + 1)];
+    __shared__ NbScratch nb_scratch[GPB];
+    __shared__ double keep_all[GPB][sep_keep_doubles<SB, false, false>()];
+    __shared__ SepRowsLds<SB, CB> rows_lds[BS];
+    __shared__ double bconst_all[GPB][16 * 2 * SEP_D * SB + 8 * SEP_D * SB];
+    const int gl = threadIdx.x & 15;
+    const int gib = threadIdx.x / 16;
+    lds_poison();
+    kclock_start(args);
+    grid_clear<BS>(args);
+    const int ai = xcd_block((int)blockIdx.x, (int)gridDim.x) * GPB + gib;
+    if (ai >= args.num_agents) return;
+    impc_sep_agent<SB, CB, false, false, false, false, true>(op, buf, args, ai, gl, stage_all[gib], red_all[gib],
+                                                             nb_scratch[gib], keep_all[gib], rows_lds + gib * 16,
+                                                             bconst_all[gib], nullptr, StoreArgs{nullptr, 0}, conn);
+    kclock_end<BS>(args);
+}
+#endif  // MPCCBF_CONN_TU
 
 // ---------------------------------------------------------------------------------------------
 // One agent per wave (impc_wide.hpp)
@@ -1388,6 +1428,8 @@ hipError_t launch_impc_store(const DevOps& op, const double* buf, const ImpcArgs
     hipLaunchKernelGGL((dev::impc_wide_store_kernel<BS>), dim3(blocks), dim3(BS), 0, s, op, buf, a, st);
     return hipGetLastError();
 }
+#elif defined(MPCCBF_CONN_TU)
+// (impc_conn.hip: the connectivity launch and the per-team spectrum launch)
 #else
 
 template <int NZ, int G, int R>

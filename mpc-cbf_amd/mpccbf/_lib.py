@@ -23,7 +23,7 @@ EXPORTED = [
     "mpccbf_comm_create", "mpccbf_comm_destroy", "mpccbf_kernel_name", "mpccbf_fov_control_solve",
     "mpccbf_connectivity_control_solve", "mpccbf_host_operators", "mpccbf_host_last_error",
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
-    "mpccbf_set_active_store", "mpccbf_cap_audit_run",
+    "mpccbf_set_active_store", "mpccbf_cap_audit_run", "mpccbf_set_connectivity",
 ]
 
 # active-set store (mpccbf_set_active_store): int32 words per record, side keys per record
@@ -167,6 +167,12 @@ class CapAudit(C.Structure):
                 ("x0_out", C.c_void_p), ("tol", C.c_double)]
 
 
+class Connectivity(C.Structure):
+    _fields_ = [("d_max", C.c_double), ("lambda2_min", C.c_double), ("lambda2_switch", C.c_double),
+                ("num_teams", C.c_int32), ("team_ptr", C.c_void_p), ("lambda2", C.c_void_p),
+                ("fiedler", C.c_void_p)]
+
+
 class Run(C.Structure):
     _fields_ = [("num_steps", C.c_int32), ("states_alt", C.c_void_p), ("status_log", C.c_void_p),
                 ("iters_log", C.c_void_p), ("step_ms", C.c_void_p), ("solve_ms", C.c_void_p),
@@ -219,6 +225,8 @@ def load():
         L.mpccbf_set_active_store.argtypes = [vp, vp, C.c_int32, C.c_int32]
     if hasattr(L, "mpccbf_cap_audit_run"):
         L.mpccbf_cap_audit_run.argtypes = [vp, C.POINTER(Batch), C.POINTER(CapAudit), vp]
+    if hasattr(L, "mpccbf_set_connectivity"):
+        L.mpccbf_set_connectivity.argtypes = [vp, C.POINTER(Connectivity)]
     L.mpccbf_build_neighbors.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_double, vp, vp, vp]
     L.mpccbf_qp_solve_dense.argtypes = [C.POINTER(DenseQP), vp, vp, vp]
@@ -314,6 +322,7 @@ class Context:
         self.k_hor = int(cfg["k_hor"])
         self.device = device
         self._active_store = None
+        self._connectivity = None
         self._last_knn = (0, 0.0)  # the neighbour query of the last solve (audit_neighbors' default)
 
     def close(self):
@@ -352,6 +361,37 @@ class Context:
             raise MpccbfError("the active store must be contiguous")
         _check(load().mpccbf_set_active_store(self._h, store.data_ptr(), int(store.shape[0]), int(min_steps)))
         self._active_store = store
+
+    def set_connectivity(self, team_ptr, d_max=None, lambda2_min=0.1, lambda2_switch=0.1, lambda2=None,
+                         fiedler=None):
+        """Attach the connectivity-maintenance rows (mpccbf_set_connectivity), or detach with
+        team_ptr None. team_ptr: host integers, num_teams + 1 non-decreasing offsets into the rows of
+        the state table (team t = rows team_ptr[t] .. team_ptr[t+1]-1, 2 .. 16 members); d_max: the
+        connectivity range. lambda2 (num_teams) / fiedler (team_ptr[-1] - team_ptr[0]): optional
+        float64 device tensors every later step writes its teams' lambda2 and Fiedler entries
+        into; the context keeps a reference to them while attached."""
+        if team_ptr is None:
+            _check(load().mpccbf_set_connectivity(self._h, None))
+            self._connectivity = None
+            return
+        if d_max is None:
+            raise MpccbfError("set_connectivity needs d_max")
+        tp = np.ascontiguousarray(np.asarray(team_ptr).reshape(-1), dtype=np.int32)
+        if tp.size < 1:
+            raise MpccbfError("team_ptr needs at least one offset")
+        import torch
+        for name, t, size in (("lambda2", lambda2, tp.size - 1), ("fiedler", fiedler, int(tp[-1]) - int(tp[0]))):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+                raise MpccbfError(f"{name} must be a contiguous float64 device tensor")
+            if t.numel() < size:
+                raise MpccbfError(f"{name} needs {size} entries")
+        k = Connectivity(d_max=float(d_max), lambda2_min=float(lambda2_min), lambda2_switch=float(lambda2_switch),
+                         num_teams=int(tp.size - 1), team_ptr=tp.ctypes.data, lambda2=_ptr(lambda2),
+                         fiedler=_ptr(fiedler))
+        _check(load().mpccbf_set_connectivity(self._h, C.byref(k)))
+        self._connectivity = (tp, lambda2, fiedler)
 
     def alloc_active_store(self, num_states: int, device=None):
         """A zero-filled (num_states, 8) int32 store (no records) for set_active_store."""

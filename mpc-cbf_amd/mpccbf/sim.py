@@ -61,11 +61,16 @@ class Simulator:
     audit: after every step, the neighbour-cap audit of that step's solve (Context.audit_neighbors):
     self.audit_log gets one mpccbf.audit_summary per step, self.audit_counts / self.audit_excess hold
     the last step's counts (device, n x 8) and largest scaled excesses (n x 2). Collision controller without slack variables, Jacobi order. Statuses,
-    trajectories and states_json() are those of audit=False."""
+    trajectories and states_json() are those of audit=False.
+    teams / d_max: attach the connectivity-maintenance rows (Context.set_connectivity; teams = the
+    team_ptr offsets into the robots, lambda2_min / lambda2_switch as there); self.lambda2_log gets
+    one array per step, the lambda2 of every team at the states that step planned from. Collision
+    controller without slack variables, Jacobi order, no audit."""
 
     def __init__(self, cfg: dict, states: np.ndarray, targets: np.ndarray, *, neighbours="knn",
                  knn_k=8, knn_radius=None, pos_std=0.0, vel_std=0.0, noise_seed=0, device=0,
-                 record=True, order="jacobi", warm=False, audit=False):
+                 record=True, order="jacobi", warm=False, audit=False, teams=None, d_max=None,
+                 lambda2_min=0.1, lambda2_switch=0.1):
         import torch
         if order not in ("jacobi", "gauss_seidel"):
             raise ValueError("order must be 'jacobi' or 'gauss_seidel'")
@@ -73,6 +78,10 @@ class Simulator:
             raise ValueError("audit=True needs order='jacobi'")
         if audit and (cfg.get("cbf_mode", 0) == 1 or cfg.get("slack_mode", 0)):
             raise ValueError("audit=True needs the collision controller without slack variables")
+        if teams is not None and (order != "jacobi" or audit):
+            raise ValueError("teams needs order='jacobi' and audit=False")
+        if teams is not None and d_max is None:
+            raise ValueError("teams needs d_max")
         self.order = order
         self.torch = torch
         self.cfg = dict(cfg)
@@ -105,6 +114,13 @@ class Simulator:
         self.audit_counts = None
         self.audit_excess = None
         self.nb_out = torch.full((n, 16), -1, dtype=torch.int32, device=self.dev) if audit else None
+        self.lambda2_log = []
+        self.lambda2 = None
+        if teams is not None:
+            self.lambda2 = torch.zeros((max(len(teams) - 1, 1),), dtype=torch.float64, device=self.dev)
+            self.ctx.set_connectivity(teams, d_max, lambda2_min=lambda2_min, lambda2_switch=lambda2_switch,
+                                      lambda2=self.lambda2)
+            self.num_teams = len(teams) - 1
         self.gs_next = torch.empty((1, 6), dtype=torch.float64, device=self.dev)
         self.noise = dict(pos_std=pos_std, vel_std=vel_std, noise_seed=noise_seed)
         self.step_index = 0
@@ -147,6 +163,8 @@ class Simulator:
         torch.cuda.synchronize()
         status = o["status"].cpu().numpy()
         self.status_log.append(status.copy())
+        if self.lambda2 is not None:
+            self.lambda2_log.append(self.lambda2.cpu().numpy()[:self.num_teams].copy())
         if self.record:
             self._record(t_before, status)
         self.states, self.next = self.next, self.states

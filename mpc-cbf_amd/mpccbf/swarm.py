@@ -163,3 +163,61 @@ def all_csr(n: int):
     col = np.concatenate([np.delete(np.arange(n), i) for i in range(n)]).astype(np.int32) \
         if n > 1 else np.zeros(0, np.int32)
     return row_ptr, col
+
+
+def team_swarm(sizes, spacing: float = 2.5, seed: int = SEED, shape: str = "ring", pos_noise: float = 0.05,
+               speed=(0.5, 2.0), vel_noise: float = 0.3, target_scale: float = 3.0, gap: float = 30.0):
+    """Teams for the connectivity rows (Context.set_connectivity): team t has sizes[t] members in
+    consecutive rows, on a ring whose neighbouring members are `spacing` apart (shape "ring") or on
+    a line ("line") or a square lattice ("grid") with that spacing (shape may also be a list, one
+    entry per team), positions with
+    N(0, pos_noise) noise, every member moving away from its team's centre at one speed per team
+    drawn from U(speed) plus N(0, vel_noise) noise, its target at target_scale times its offset from
+    the centre. Team centres are `gap` apart along x, so teams do not interact. Seeded. Returns
+    (states N x 6, targets N x 3, team_ptr int32 len(sizes) + 1)."""
+    rng = np.random.default_rng(seed)
+    sizes = [int(v) for v in sizes]
+    shapes = [shape] * len(sizes) if isinstance(shape, str) else list(shape)
+    team_ptr = np.zeros(len(sizes) + 1, dtype=np.int32)
+    team_ptr[1:] = np.cumsum(sizes)
+    n = int(team_ptr[-1])
+    states, targets = np.zeros((n, 6)), np.zeros((n, 3))
+    for t, m in enumerate(sizes):
+        if m == 0:
+            continue
+        if shapes[t] == "ring":
+            rad = 0.0 if m == 1 else spacing / (2.0 * math.sin(math.pi / m))
+            ang = 2.0 * math.pi * np.arange(m) / m + rng.uniform(0.0, 2.0 * math.pi)
+            off = rad * np.stack([np.cos(ang), np.sin(ang)], axis=1)
+        elif shapes[t] == "line":
+            off = np.stack([spacing * (np.arange(m) - 0.5 * (m - 1)), np.zeros(m)], axis=1)
+        elif shapes[t] == "grid":
+            side = int(math.ceil(math.sqrt(m)))
+            idx = np.arange(m)
+            off = spacing * np.stack([idx % side - 0.5 * (side - 1), idx // side - 0.5 * (side - 1)], axis=1)
+        else:
+            raise ValueError(f"unknown team shape: {shapes[t]}")
+        norm = np.linalg.norm(off, axis=1, keepdims=True)
+        out = np.divide(off, norm, out=np.zeros_like(off), where=norm > 0)
+        centre = np.array([gap * t, 0.0])
+        r = slice(int(team_ptr[t]), int(team_ptr[t + 1]))
+        states[r, :2] = centre + off + rng.normal(0.0, pos_noise, (m, 2))
+        states[r, 3:5] = rng.uniform(speed[0], speed[1]) * out + rng.normal(0.0, vel_noise, (m, 2))
+        targets[r, :2] = centre + target_scale * off
+    return states, targets, team_ptr
+
+
+def team_csr(team_ptr):
+    """Neighbour lists with the reference's semantics inside every team: each member lists all
+    other members of its team (rows outside every team list nobody). Returns (row_ptr, col)."""
+    team_ptr = np.asarray(team_ptr, dtype=np.int64)
+    n = int(team_ptr[-1])
+    rows = [np.zeros(0, np.int64)] * n
+    for t in range(len(team_ptr) - 1):
+        mem = np.arange(team_ptr[t], team_ptr[t + 1])
+        for i in mem:
+            rows[i] = mem[mem != i]
+    row_ptr = np.zeros(n + 1, dtype=np.int32)
+    row_ptr[1:] = np.cumsum([len(r) for r in rows])
+    col = np.concatenate(rows).astype(np.int32) if row_ptr[-1] else np.zeros(0, np.int32)
+    return row_ptr, col

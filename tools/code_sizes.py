@@ -19,7 +19,8 @@ PKG = os.path.join(REPO, "mpc-cbf_amd")
 LLVM = "/opt/rocm/llvm/bin"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
          "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form"]
-SRCS = ["csrc/kernels/impc_kernel.hip", "csrc/kernels/impc_store.hip"]
+SRCS = ["csrc/kernels/impc_kernel.hip", "csrc/kernels/impc_store.hip", "csrc/kernels/impc_conn.hip",
+        "csrc/kernels/connectivity_control.hip"]
 
 
 def device_code(src):

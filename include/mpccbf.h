@@ -605,6 +605,35 @@ typedef struct mpccbf_host_ops {
 int mpccbf_host_operators(const mpccbf_params* p, int32_t keep_redundant, mpccbf_host_ops* out);
 const char* mpccbf_host_last_error(void);
 
+/* Host-only inspection of the launch plan and the operator packing (no device needed; used by the
+ * CPU tests; MPCCBF_ABI_VERSION is unchanged: no struct changed layout). For a context created from
+ * (params, options; options NULL = defaults) on a device whose share-adaptive threshold is wide_max
+ * (4 x its compute units; mpccbf_create's own), with this variant, an active store and connectivity
+ * attached or not: what mpccbf_kernel_name and mpccbf_impc_launch_waves report after a solve of
+ * num_agents agents with caller lists (csr) or the k nearest (knn_k), whether that launch reads
+ * the store and defers agents, the capacity launch that follows ("": none), and the layout of the
+ * operator buffer. The strings are static. buf: NULL, or buf_capacity doubles that receive the
+ * buffer's head (call once for `total`). offsets: every operator's offset into the buffer. */
+#define MPCCBF_HOST_PLAN_OFFSETS 38
+typedef struct mpccbf_host_plan {
+    const char* kernel_name;
+    const char* capacity_name;
+    int32_t block_size, agents_per_block; /* the main launch: ceil(num_agents / agents_per_block) blocks */
+    int32_t clock_waves;
+    int32_t store, defers;
+    int32_t hot, total;        /* doubles: the prefix of the separable collision kernels' operators, all */
+    int32_t wide_capacity;     /* the largest `hot` the one-agent-per-wave kernel stages */
+    int32_t sep, sep_rows_per_dim, sep_sb, o_Gsep; /* separable layout: 3 x sep_sb x 16 rows of 10 doubles
+                                  [g0 g1 | Gs(6) | lo hi] at o_Gsep, channel-major, row f of a channel in
+                                  slot f / 16, lane f % 16; unused rows are g = 0, [-1, 1] */
+    int32_t offsets[MPCCBF_HOST_PLAN_OFFSETS];
+    double* buf;
+    int32_t buf_capacity;
+} mpccbf_host_plan;
+int mpccbf_host_launch_plan(const mpccbf_params* p, const mpccbf_options* opt, int32_t variant,
+                            int32_t num_agents, int32_t csr, int32_t knn_k, int32_t store,
+                            int32_t connectivity, int32_t wide_max, mpccbf_host_plan* out);
+
 /* Diagnostics */
 const char* mpccbf_last_error(void);
 const char* mpccbf_status_string(int32_t status); /* SolveStatusToStr, Solver.cpp:4-28 */

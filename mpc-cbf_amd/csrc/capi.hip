@@ -18,40 +18,14 @@
 #include "../../include/mpccbf.h"
 #include "host/errors.hpp"
 #include "host/operators.hpp"
+#include "host/pack_operators.hpp"
 #include "kernels/impc.hpp"
 #include "kernels/cap_audit.hpp"
 #include "kernels/cbf_control.hpp"
 #include "kernels/conn_rows.hpp"
-#include "kernels/fov_cbf.hpp"
+#include "kernels/launch_plan.hpp"
 
 namespace mpccbf {
-
-hipError_t launch_impc(const DevOps& op, const double* buf, const ImpcArgs& a, int variant,
-                       hipStream_t s, const StoreArgs& st);
-const char* impc_kernel_name(const DevOps& op, int variant, int n, bool store);
-bool impc_store_ok(const DevOps& op, int variant, int n);
-int impc_clock_waves(const DevOps& op, int variant, int n);
-hipError_t launch_impc_fov(const DevOps& op, const double* buf, const ImpcArgs& a, hipStream_t s);
-hipError_t launch_fov_rows_eval(int count, const double* ego, const double* nb, double fov, double Ds, double Rs,
-                                double bbx, double bby, double* vor, double* rows, hipStream_t s);
-hipError_t launch_impc_fallback(const DevOps& op, const double* buf, const ImpcArgs& a, bool wide,
-                                hipStream_t s, const StoreArgs& st);
-bool impc_may_defer(const DevOps& op, int variant, bool csr, int knn_k, int n);
-bool impc_rows_may_exceed(const DevOps& op, bool csr, int knn_k);
-int launch_neighbors(const double* states, int num_states, int first, int num_agents, int k,
-                     double radius, int32_t* row_ptr, int32_t* col, void* scratch,
-                     size_t scratch_bytes, hipStream_t s);
-size_t neighbors_scratch_bytes(int num_states, int num_agents, int k);
-size_t grid_table_bytes(int num_states);
-hipError_t launch_cap_audit(const DevOps& op, const double* buf, const AuditArgs& a, hipStream_t s);
-hipError_t launch_team_spectrum(const SpectrumArgs& a, hipStream_t s);
-hipError_t launch_impc_conn(const DevOps& op, const double* buf, const ImpcArgs& a, const ConnArgs& cn, hipStream_t s);
-bool impc_conn_ok(const DevOps& op);
-const char* impc_conn_kernel_name();
-int impc_conn_clock_waves(int n);
-void grid_table_carve(void* base, int num_states, uint32_t** cnt, uint32_t** slots, double** sst);
-hipError_t launch_grid_insert(const double* states, int n, int skip0, int skip1, double radius,
-                              uint32_t* cnt, uint32_t* slots, double* sst, hipStream_t s);
 
 static thread_local std::string g_err;
 
@@ -68,6 +42,32 @@ static int fail(int code, const std::string& msg) { return set_error(code, msg);
         if (e_ != hipSuccess) return fail(MPCCBF_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
 
+// A device allocation that grows on demand and is freed with its owner. After a failed growth it
+// is empty (bytes == 0), so the next call allocates again.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    // at least `need` bytes (a buffer that has to grow is reallocated: its contents are gone)
+    hipError_t reserve(size_t need) {
+        if (need <= bytes) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&p, need);
+        if (e == hipSuccess) bytes = need; else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
 }  // namespace mpccbf
 
 struct mpccbf_ctx {
@@ -77,15 +77,12 @@ struct mpccbf_ctx {
     mpccbf::Operators ops;
     mpccbf::DevOps dev;
     int device = 0;
-    double* dbuf = nullptr;
-    size_t dbuf_elems = 0;
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    void* grid_scratch = nullptr;  // three neighbour tables (see GridArgs)
-    size_t grid_bytes = 0;
+    mpccbf::DevBuf dbuf;          // the packed operators (pack_operators)
+    mpccbf::DevBuf scratch;       // mpccbf_build_neighbors
+    mpccbf::DevBuf grid_scratch;  // three neighbour tables (see GridArgs)
     // fallback queues [count, -, agents...], two (alternating by enqueue parity: the main launch
     // zeroes the other one's header), zero-initialised
-    int32_t* defer = nullptr;
+    mpccbf::DevBuf defer;
     int defer_cap = 0;
     int defer_parity = 0;
     int variant = 0;
@@ -98,8 +95,7 @@ struct mpccbf_ctx {
     // neighbour-cap audit (mpccbf_cap_audit_run): the second-derivative basis' offset in dbuf, and
     // the scratch its iteration-0 launch writes (x0: agents x n doubles, then their statuses)
     int32_t o_EB2 = 0;
-    void* audit_scratch = nullptr;
-    size_t audit_bytes = 0;
+    mpccbf::DevBuf audit_scratch;
     // grid mode: where the previous mpccbf_run_steps call left the table rotation (ABI 12,
     // mpccbf_run::continue_tables): its final state table, shape, query and the next step's table
     // connectivity rows (mpccbf_set_connectivity): the teams (host copy), the caller's outputs, and
@@ -112,11 +108,8 @@ struct mpccbf_ctx {
         double* out_l2 = nullptr;
         double* out_fiedler = nullptr;
         int rows = 0;
-        int32_t* d_team_ptr = nullptr;
-        int32_t* d_team_mode = nullptr;
-        int32_t* d_row_team = nullptr;
-        double* d_team_l2 = nullptr;
-        double* d_fiedler = nullptr;
+        mpccbf::DevBuf d_team_ptr, d_team_mode, d_row_team;  // int32
+        mpccbf::DevBuf d_team_l2, d_fiedler;                 // double
     } conn;
     struct {
         bool valid = false;
@@ -128,57 +121,28 @@ struct mpccbf_ctx {
 
 using namespace mpccbf;
 
-// The operators as the launches see them: while a store is attached the 16-lane layout runs its
-// full kernel (the lean main launch has no store instantiation; statuses and solutions are the
-// same, the lean launch only defers what it does not finish to the full pipeline)
-static DevOps launch_ops(const mpccbf_ctx* c) {
-    DevOps d = c->dev;
-    if (c->store) d.lean = 0;
-    return d;
+// The launch plan of the context's next IMPC step for n agents (launch_plan.hpp)
+static LaunchPlan ctx_plan(const mpccbf_ctx* c, int n, bool csr, int knn_k, bool store) {
+    return impc_launch_plan(c->dev, c->variant, n, csr, knn_k, store, c->conn.on);
 }
 
 // Warm-start threshold when mpccbf_set_active_store is given min_steps = 0
 constexpr int STORE_MIN_STEPS_DEFAULT = 3;
 
-static void pack(std::vector<double>& v, int32_t& off, const Mat& m) {
-    off = (int32_t)v.size();
-    v.insert(v.end(), m.a.begin(), m.a.end());
-}
-static void pack(std::vector<double>& v, int32_t& off, const std::vector<double>& m) {
-    off = (int32_t)v.size();
-    v.insert(v.end(), m.begin(), m.end());
-}
-static void pack(std::vector<double>& v, int32_t& off, const std::vector<Mat>& ms) {
-    off = (int32_t)v.size();
-    for (const Mat& m : ms) v.insert(v.end(), m.a.begin(), m.a.end());
-}
-
 // The three neighbour tables of grid mode in ctx scratch (grown on demand).
 static int grid_tables(mpccbf_ctx* c, int num_states, uint32_t* (&cnt)[3], uint32_t* (&slots)[3],
                        double* (&sst)[3]) {
     const size_t tb = grid_table_bytes(num_states);
-    if (3 * tb > c->grid_bytes) {
-        c->gcont.valid = false;
-        if (c->grid_scratch) (void)hipFree(c->grid_scratch);
-        c->grid_scratch = nullptr;
-        c->grid_bytes = 0;
-        HIP_TRY(hipMalloc(&c->grid_scratch, 3 * tb));
-        c->grid_bytes = 3 * tb;
-    }
+    if (3 * tb > c->grid_scratch.bytes) c->gcont.valid = false;  // (the tables a continuation would read go)
+    HIP_TRY(c->grid_scratch.reserve(3 * tb));
     for (int t = 0; t < 3; t++)
-        grid_table_carve((char*)c->grid_scratch + t * tb, num_states, &cnt[t], &slots[t], &sst[t]);
+        grid_table_carve(c->grid_scratch.as<char>() + t * tb, num_states, &cnt[t], &slots[t], &sst[t]);
     return MPCCBF_OK;
 }
 
 static void conn_free(mpccbf_ctx* c) {
     auto& k = c->conn;
-    if (k.d_team_ptr) (void)hipFree(k.d_team_ptr);
-    if (k.d_team_mode) (void)hipFree(k.d_team_mode);
-    if (k.d_row_team) (void)hipFree(k.d_row_team);
-    if (k.d_team_l2) (void)hipFree(k.d_team_l2);
-    if (k.d_fiedler) (void)hipFree(k.d_fiedler);
-    k.d_team_ptr = k.d_team_mode = k.d_row_team = nullptr;
-    k.d_team_l2 = k.d_fiedler = nullptr;
+    for (DevBuf* b : {&k.d_team_ptr, &k.d_team_mode, &k.d_row_team, &k.d_team_l2, &k.d_fiedler}) b->release();
     k.rows = 0;
 }
 
@@ -186,23 +150,23 @@ static void conn_free(mpccbf_ctx* c) {
 // and the rows' teams are uploaded here, the rest is written by every step's spectrum launch).
 static int conn_tables(mpccbf_ctx* c, int num_states) {
     auto& k = c->conn;
-    if (k.d_team_ptr && k.rows >= num_states) return MPCCBF_OK;
+    if (k.d_team_ptr.p && k.rows >= num_states) return MPCCBF_OK;
     conn_free(c);
     const size_t nt = k.team_ptr.size() - 1, rows = (size_t)std::max(num_states, 1);
-    HIP_TRY(hipMalloc(&k.d_team_ptr, (nt + 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&k.d_team_mode, std::max<size_t>(nt, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&k.d_team_l2, std::max<size_t>(nt, 1) * sizeof(double)));
-    HIP_TRY(hipMalloc(&k.d_row_team, rows * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&k.d_fiedler, rows * sizeof(double)));
+    HIP_TRY(k.d_team_ptr.reserve((nt + 1) * sizeof(int32_t)));
+    HIP_TRY(k.d_team_mode.reserve(std::max<size_t>(nt, 1) * sizeof(int32_t)));
+    HIP_TRY(k.d_team_l2.reserve(std::max<size_t>(nt, 1) * sizeof(double)));
+    HIP_TRY(k.d_row_team.reserve(rows * sizeof(int32_t)));
+    HIP_TRY(k.d_fiedler.reserve(rows * sizeof(double)));
     std::vector<int32_t> row_team(rows, -1);
     for (size_t t = 0; t < nt; t++)
         if (k.team_ptr[t + 1] - k.team_ptr[t] >= 2)  // (teams of one: no rows)
             for (int32_t r = k.team_ptr[t]; r < k.team_ptr[t + 1] && r < num_states; r++) row_team[r] = (int32_t)t;
-    HIP_TRY(hipMemcpy(k.d_team_ptr, k.team_ptr.data(), (nt + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(k.d_row_team, row_team.data(), rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(k.d_team_mode, 0, std::max<size_t>(nt, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMemset(k.d_team_l2, 0, std::max<size_t>(nt, 1) * sizeof(double)));
-    HIP_TRY(hipMemset(k.d_fiedler, 0, rows * sizeof(double)));
+    HIP_TRY(hipMemcpy(k.d_team_ptr.p, k.team_ptr.data(), (nt + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.d_row_team.p, row_team.data(), rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(k.d_team_mode.p, 0, k.d_team_mode.bytes));
+    HIP_TRY(hipMemset(k.d_team_l2.p, 0, k.d_team_l2.bytes));
+    HIP_TRY(hipMemset(k.d_fiedler.p, 0, k.d_fiedler.bytes));
     k.rows = (int)rows;
     return MPCCBF_OK;
 }
@@ -211,8 +175,9 @@ static int conn_tables(mpccbf_ctx* c, int num_states) {
 // IMPC kernel alone. Grid mode: gstep < 0 builds table 0 from b->states first (memset + insert
 // kernel); gstep >= 0 (mpccbf_run_steps) reads table gstep % 3, which the previous step filled,
 // has the kernel insert its next states into table (gstep + 1) % 3 and zero table (gstep + 2) % 3.
+// ops / store: the context's (c->dev, c->store), or what the cap audit puts in their place.
 int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                 int gstep = -1, unsigned long long* kclock = nullptr) {
+                 const DevOps& ops, int32_t* store, int gstep = -1, unsigned long long* kclock = nullptr) {
     if (!c || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
     // any step outside a grid-mode mpccbf_run_steps rotation (mpccbf_impc_solve, the CSR steps of
     // mpccbf_run_steps) may write the state table a continuation would read: it must rebuild
@@ -232,7 +197,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "traj_t (closed-loop fallback) needs the persistent x buffer");
     if (!(b->pos_std >= 0.0) || !(b->vel_std >= 0.0))
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "noise standard deviations must be >= 0");
-    if (c->store && c->store_rows < b->num_states)
+    if (store && c->store_rows < b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows (" + std::to_string(c->store_rows) +
                                                      ") < num_states (" + std::to_string(b->num_states) + ")");
     const bool conn = c->conn.on;
@@ -240,7 +205,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr ends at row " +
                                                      std::to_string(c->conn.team_ptr.back()) + " > num_states (" +
                                                      std::to_string(b->num_states) + ")");
-    const DevOps dops = launch_ops(c);
+    const LaunchPlan plan = impc_launch_plan(ops, c->variant, b->num_agents, !grid, b->knn_k, store != nullptr, conn);
     ImpcArgs a;
     std::memset(&a, 0, sizeof(a));
     HIP_TRY(hipSetDevice(c->device));
@@ -254,23 +219,23 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         SpectrumArgs sp;
         std::memset(&sp, 0, sizeof(sp));
         sp.num_teams = (int32_t)k.team_ptr.size() - 1;
-        sp.team_ptr = k.d_team_ptr;
+        sp.team_ptr = k.d_team_ptr.as<int32_t>();
         sp.states = b->states;
         sp.first = b->agent_first;
         sp.count = b->num_agents;
         sp.dmax = k.dmax;
         sp.l2_switch = k.l2_switch;
-        sp.team_l2 = k.d_team_l2;
-        sp.team_mode = k.d_team_mode;
-        sp.fiedler = k.d_fiedler;
+        sp.team_l2 = k.d_team_l2.as<double>();
+        sp.team_mode = k.d_team_mode.as<int32_t>();
+        sp.fiedler = k.d_fiedler.as<double>();
         sp.out_l2 = k.out_l2;
         sp.out_fiedler = k.out_fiedler;
         HIP_TRY(launch_team_spectrum(sp, stream));
-        cn.row_team = k.d_row_team;
-        cn.team_ptr = k.d_team_ptr;
-        cn.team_mode = k.d_team_mode;
-        cn.team_l2 = k.d_team_l2;
-        cn.fiedler = k.d_fiedler;
+        cn.row_team = k.d_row_team.as<int32_t>();
+        cn.team_ptr = sp.team_ptr;
+        cn.team_mode = sp.team_mode;
+        cn.team_l2 = sp.team_l2;
+        cn.fiedler = sp.fiedler;
         cn.dmax = k.dmax;
         cn.l2_min = k.l2_min;
     }
@@ -300,7 +265,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         a.grid.radius = b->knn_radius;
         a.grid.k = b->knn_k;
         // FoV controller: only agents inside the field of view are observed neighbours
-        a.grid.cone = (c->dev.cbf_mode == 1 && c->dev.fov_beta < 2.0 * M_PI - 1e-9) ? 0.5 * c->dev.fov_beta : 0.0;
+        a.grid.cone = (ops.cbf_mode == 1 && ops.fov_beta < 2.0 * M_PI - 1e-9) ? 0.5 * ops.fov_beta : 0.0;
     }
     a.num_states = b->num_states;
     a.states = b->states;
@@ -333,39 +298,39 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     // phase 1; beyond the separable kernel's 16 CBF row slots) are solved by a second launch of
     // the full separable pipeline (128 slots when the 16 can be exceeded)
     // (the connectivity launch has no capacity launch behind it: beyond its rows, ERROR)
-    const bool fb = !conn && c->dev.cbf_mode != 1 && impc_may_defer(dops, c->variant, !grid, b->knn_k, b->num_agents);
+    const bool fb = plan.defer;
     // the store: read and written by the kernels that support it; any other launch leaves its
     // agents' records zero (no record), so a record never outlives the solve it describes
-    StoreArgs st{nullptr, 0};
-    if (c->store) {
-        if (!conn && impc_store_ok(dops, c->variant, b->num_agents)) {
-            st.records = c->store;
-            st.min_steps = c->store_min_steps;
-        } else {
-            HIP_TRY(hipMemsetAsync(c->store + (size_t)b->agent_first * AS_WORDS, 0,
-                                   (size_t)b->num_agents * AS_WORDS * sizeof(int32_t), stream));
-        }
-    }
+    const StoreArgs st{store, c->store_min_steps};
+    if (store && !plan.store)
+        HIP_TRY(hipMemsetAsync(store + (size_t)b->agent_first * AS_WORDS, 0,
+                               (size_t)b->num_agents * AS_WORDS * sizeof(int32_t), stream));
     c->last_n = b->num_agents;
     if (fb && c->defer_cap < b->num_agents) {
-        if (c->defer) (void)hipFree(c->defer);
-        c->defer = nullptr;
+        const size_t bytes = 2 * (size_t)(b->num_agents + 2) * sizeof(int32_t);
         c->defer_cap = 0;
-        HIP_TRY(hipMalloc(&c->defer, 2 * (size_t)(b->num_agents + 2) * sizeof(int32_t)));
-        HIP_TRY(hipMemsetAsync(c->defer, 0, 2 * (size_t)(b->num_agents + 2) * sizeof(int32_t), stream));
+        HIP_TRY(c->defer.reserve(bytes));
+        HIP_TRY(hipMemsetAsync(c->defer.p, 0, bytes, stream));
         c->defer_cap = b->num_agents;
         c->defer_parity = 0;
     }
     int32_t* q_this = nullptr;
     if (fb) {
-        q_this = c->defer + (size_t)c->defer_parity * (c->defer_cap + 2);
-        a.defer_clear = c->defer + (size_t)(c->defer_parity ^ 1) * (c->defer_cap + 2);
+        q_this = c->defer.as<int32_t>() + (size_t)c->defer_parity * (c->defer_cap + 2);
+        a.defer_clear = c->defer.as<int32_t>() + (size_t)(c->defer_parity ^ 1) * (c->defer_cap + 2);
     }
     a.defer = q_this;
     if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
-    hipError_t e = conn ? launch_impc_conn(dops, c->dbuf, a, cn, stream)
-                        : (c->dev.cbf_mode == 1 ? launch_impc_fov(c->dev, c->dbuf, a, stream)
-                                                : launch_impc(dops, c->dbuf, a, c->variant, stream, st));
+    const double* buf = c->dbuf.as<double>();
+    // one launcher per translation unit that instantiates IMPC kernels (launch_plan.hpp)
+    auto launch = [&](ImpcKernel k, int bs, int per_block, const ImpcArgs& ia) {
+        const int blocks = (ia.num_agents + per_block - 1) / per_block;
+        if (k == IMPC_CONN) return launch_impc_conn(k, blocks, bs, ops, buf, ia, cn, stream);
+        if (k == IMPC_FOV || k == IMPC_FOV_SLACK) return launch_impc_fov(k, blocks, bs, ops, buf, ia, stream);
+        if (plan.store) return launch_impc_store(k, blocks, bs, ops, buf, ia, st, stream);
+        return launch_impc(k, blocks, bs, ops, buf, ia, stream);
+    };
+    hipError_t e = launch(plan.kernel, plan.block_size, plan.agents_per_block, a);
     // the queues alternate only once the main launch is enqueued: a launch that failed zeroed no
     // header, so the next call must append to this step's queue again (zeroed by the launch before)
     if (e == hipSuccess && fb) c->defer_parity ^= 1;
@@ -375,7 +340,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         f.defer_clear = nullptr;
         f.kclock = nullptr;  // (the clock is the main launch's)
         f.queue = q_this;
-        e = launch_impc_fallback(dops, c->dbuf, f, impc_rows_may_exceed(dops, !grid, b->knn_k), stream, st);
+        e = launch(plan.capacity, IMPC_QUEUE_BLOCK, IMPC_QUEUE_AGENTS, f);
         // (a queue the fallback never read is zeroed by the main launch after next)
     }
     if (e == hipSuccess && ev1) e = hipEventRecord(ev1, stream);
@@ -424,240 +389,26 @@ int mpccbf_create(const mpccbf_params* p, const mpccbf_options* opt, mpccbf_ctx*
         delete c;
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, e.what());
     }
-    const Operators& o = c->ops;
-    DevOps& d = c->dev;
-    std::memset(&d, 0, sizeof(d));
-    d.n = o.n;
-    d.nz = o.nz;
-    d.m = o.G.r;
-    d.mc = o.Cs.r;
-    d.K = o.K;
-    d.spd_f = o.spd_f;
-    d.cbf_h = o.cbf_h;
-    d.impc_iter = p->impc_iter;
-    std::vector<double> v;
-    // operator buffer: the operators of the separable kernels first (the "hot" prefix the
-    // one-agent-per-wave kernel stages in LDS, DevOps::hot), then the rest
-    // separable layout: box rows regrouped by channel, 16 per channel (lanes of a group)
-    d.sep = 0;
-    d.o_Gsep = 0;
-    if (o.sep && o.nzd == SEP_NZD_HOST) {
-        int per[DIM] = {0, 0, 0};
-        bool ok = true;
-        for (int i = 0; i < o.G.r; i++) {
-            if (o.row_dim[i] < 0 || o.row_dim[i] >= DIM) ok = false;
-            else per[o.row_dim[i]]++;
-            if (!(o.lo[i] > -1e300 && o.hi[i] < 1e300)) ok = false;  // the layout is two-sided only
-        }
-        const int rpd = std::max(per[0], std::max(per[1], per[2]));
-        const int sb = (rpd + 15) / 16;  // row slots per lane and channel
-        if (ok && sb <= 2) {
-            std::vector<double> B((size_t)DIM * sb * 16 * SEP_ROW, 0.0);
-            for (size_t r = 0; r < (size_t)DIM * sb * 16; r++) {
-                B[r * SEP_ROW + 8] = -1.0;  // inert row: 0 in [-1, 1]
-                B[r * SEP_ROW + 9] = 1.0;
-            }
-            int fill[DIM] = {0, 0, 0};
-            for (int i = 0; i < o.G.r; i++) {
-                const int dd = o.row_dim[i], f = fill[dd]++;
-                // slot f / 16, lane f % 16 (sb = 1: row f of the channel in lane f)
-                double* r = &B[((size_t)(dd * sb + f / 16) * 16 + f % 16) * SEP_ROW];
-                r[0] = o.G(i, dd * o.nzd);
-                r[1] = o.G(i, dd * o.nzd + 1);
-                for (int s = 0; s < SD; s++) r[2 + s] = o.Gs(i, s);
-                r[8] = o.lo[i];
-                r[9] = o.hi[i];
-            }
-            pack(v, d.o_Gsep, B);
-            std::vector<double> Pi((size_t)DIM * 3, 0.0);  // [[a b] [b c]]^-1 per channel
-            for (int dd = 0; dd < DIM; dd++) {
-                const int r0 = dd * o.nzd;
-                const double a = o.Pr(r0, r0), b = o.Pr(r0, r0 + 1), cc = o.Pr(r0 + 1, r0 + 1);
-                const double det = a * cc - b * b;
-                Pi[dd * 3 + 0] = cc / det;
-                Pi[dd * 3 + 1] = -b / det;
-                Pi[dd * 3 + 2] = a / det;
-            }
-            pack(v, d.o_Pinv, Pi);
-            d.sep = 1;
-            d.nzd = o.nzd;
-            d.sep_rows_per_dim = rpd;
-            d.sep_sb = sb;
-        }
-    }
-    pack(v, d.o_Z, o.Z);
-    pack(v, d.o_Xs, o.Xs);
-    pack(v, d.o_Pr, o.Pr);
-    pack(v, d.o_Qs, o.Qs);
-    pack(v, d.o_Qt, o.Qt);
-    pack(v, d.o_Qr, o.Qr);
-    pack(v, d.o_Ks, o.Ks);
-    pack(v, d.o_Kt, o.Kt);
-    pack(v, d.o_Kr, o.Kr);
-    pack(v, d.o_Cs, o.Cs);
-    pack(v, d.o_clo, o.clo);
-    pack(v, d.o_chi, o.chi);
-    pack(v, d.o_UZ, o.UZ);
-    pack(v, d.o_US, o.US);
-    pack(v, d.o_PZ, o.PZ);
-    pack(v, d.o_PS, o.PS);
-    pack(v, d.o_AZ, o.AZ);
-    pack(v, d.o_AS, o.AS);
-    d.P = p->num_pieces;
-    d.slack_mode = p->slack_mode ? 1 : 0;
-    d.slack_cost = p->slack_cost;
-    d.slack_decay = p->slack_decay_rate;
-    pack(v, d.o_EB0, o.EB0);
-    pack(v, d.o_EB1, o.EB1);
-    pack(v, d.o_cum, o.cum);
-    d.hot = (int32_t)v.size();
-    pack(v, d.o_LPr, o.LPr);
-    pack(v, d.o_G, o.G);
-    pack(v, d.o_Gs, o.Gs);
-    pack(v, d.o_lo, o.lo);
-    pack(v, d.o_hi, o.hi);
-    d.eval_step = o.eval_step;
-    {
-        const double tend = o.cum.empty() ? 0.0 : o.cum.back();
-        d.az_at_eval = (!o.cum.empty() && std::min(o.eval_step, tend) == std::min(p->h, tend)) ? 1 : 0;
-    }
-    d.Ts = p->Ts;
-    d.nsub = (int)(p->h / p->Ts);
-    // FoV controller: Voronoi operators, dense 16-wide box rows, P / LP padded to 16 x 16
-    d.cbf_mode = p->cbf_mode;
-    d.C = p->num_control_points;
-    d.fov_beta = p->fov_beta;
-    {
-        const dev::FovBorder fb = dev::fov_border(p->fov_beta);
-        d.fov_kap = fb.kap;
-        d.fov_sig = fb.sig_left;
-        d.fov_none = fb.none ? 1 : 0;
-    }
-    d.fov_Ds = p->fov_Ds;
-    d.fov_Rs = p->fov_Rs;
-    for (int k = 0; k < 3; k++) d.bbox[k] = p->bbox[k];
-    if (p->cbf_mode == 1 && o.nz <= 15) {
-        pack(v, d.o_VZ, o.VZ);
-        pack(v, d.o_VS, o.VS);
-        std::vector<double> W((size_t)o.G.r * WBOX_ROW, 0.0);
-        for (int i = 0; i < o.G.r; i++) {
-            double* r = &W[(size_t)i * WBOX_ROW];
-            for (int j = 0; j < o.nz; j++) r[j] = o.G(i, j);
-            for (int s2 = 0; s2 < SD; s2++) r[16 + s2] = o.Gs(i, s2);
-            r[22] = o.lo[i];
-            r[23] = o.hi[i];
-        }
-        pack(v, d.o_Wbox, W);
-        std::vector<double> P16(256, 0.0), L16(256, 0.0);
-        for (int a = 0; a < 16; a++)
-            for (int b = 0; b < 16; b++) {
-                const bool in = a < o.nz && b < o.nz;
-                P16[a * 16 + b] = in ? o.Pr(a, b) : (a == b ? 1.0 : 0.0);
-                L16[a * 16 + b] = in ? o.LPr(a, b) : (a == b ? 1.0 : 0.0);
-            }
-        pack(v, d.o_P16, P16);
-        pack(v, d.o_LP16, L16);
-        // P^-1 (padded with the identity) for the dual active-set solve: columns of
-        // L^-T L^-1 e_b by forward / backward substitution with the factor L = LPr
-        std::vector<double> Pi16(256, 0.0);
-        for (int b = 0; b < 16; b++) {
-            if (b >= o.nz) {
-                Pi16[b * 16 + b] = 1.0;
-                continue;
-            }
-            std::vector<double> x(o.nz, 0.0);
-            for (int a = 0; a < o.nz; a++) {  // L x = e_b
-                double s = a == b ? 1.0 : 0.0;
-                for (int k = 0; k < a; k++) s -= o.LPr(a, k) * x[k];
-                x[a] = s / o.LPr(a, a);
-            }
-            for (int a = o.nz - 1; a >= 0; a--) {  // L^T x = x
-                double s = x[a];
-                for (int k = a + 1; k < o.nz; k++) s -= o.LPr(k, a) * x[k];
-                x[a] = s / o.LPr(a, a);
-            }
-            for (int a = 0; a < o.nz; a++) Pi16[a * 16 + b] = x[a];
-        }
-        pack(v, d.o_Pinv16, Pi16);
-        std::vector<double> wb(o.G.r, 0.0);  // the box rows' weights in the active-set candidate rule
-        for (int i = 0; i < o.G.r; i++) {
-            double n2 = 0.0;
-            for (int a = 0; a < o.nz; a++)
-                for (int b = 0; b < o.nz; b++) n2 += o.G(i, a) * Pi16[a * 16 + b] * o.G(i, b);
-            wb[i] = 1.0 / std::sqrt(std::max(n2, 1e-30));
-        }
-        pack(v, d.o_wbox, wb);
-        auto pgram = [&](const Mat& A, int i, int j) {  // A_i P^-1 A_j^T
-            double g = 0.0;
-            for (int a = 0; a < o.nz; a++)
-                for (int b = 0; b < o.nz; b++) g += A(i, a) * Pi16[a * 16 + b] * A(j, b);
-            return g;
-        };
-        std::vector<double> wv, wf;
-        for (const Mat& V : o.VZ) {
-            wv.push_back(pgram(V, 0, 0));
-            wv.push_back(pgram(V, 0, 1));
-            wv.push_back(pgram(V, 1, 1));
-        }
-        for (const Mat& U : o.UZ)
-            for (int i = 0; i < 3; i++)
-                for (int j = i; j < 3; j++) wf.push_back(pgram(U, i, j));
-        pack(v, d.o_wvor, wv);
-        pack(v, d.o_wfov, wf);
-    }
-    pack(v, c->o_EB2, o.EB2);  // (after every operator of the solve kernels: their offsets stay)
-    v.push_back(0.0);  // keep every offset addressable even for empty operators
-    for (int i = 0; i < 3; i++) {
-        d.a_lo[i] = o.a_lo[i];
-        d.a_hi[i] = o.a_hi[i];
-    }
-    d.d_min = p->d_min;
-    d.cbf_filter = c->opt.no_cbf_filter ? 0 : 1;
-    d.maxit = c->opt.max_pdip_iters > 0 ? c->opt.max_pdip_iters : 60;
-    d.tol = c->opt.tolerance > 0 ? c->opt.tolerance : 1e-9;
-    // solver pipeline: from mpccbf_options only (zero = default)
-    const mpccbf_options& so = c->opt;
-    d.warm_delta = so.warm_delta == 0.0 ? 0.3 : (so.warm_delta > 0.0 ? so.warm_delta : 0.0);
-    d.feas_tol = 1e-6;  // CPLEX default feasibility tolerance
-    d.early_it = so.early_it == 0 ? 10 : (so.early_it > 0 ? so.early_it : 0);
-    d.fast_start = so.no_fast_start ? 0 : 1;
-    d.dual_as = so.dual_as_steps == 0 ? 24 : (so.dual_as_steps > 0 ? so.dual_as_steps : 0);
-    d.lean = so.lean ? 1 : 0;  // measured no faster at occupancy 1
-    d.das_warm = so.das_warm_steps == 0 ? 3 : (so.das_warm_steps > 0 ? so.das_warm_steps : 0);
-#ifdef MPCCBF_DIAG_ENV
-    {  // diagnostics build only (make diag): tuning overrides from the environment
-        const char* e = getenv("MPCCBF_EARLY_IT");
-        if (e) d.early_it = atoi(e);
-        const char* f = getenv("MPCCBF_FAST_START");
-        if (f) d.fast_start = atoi(f);
-        const char* g = getenv("MPCCBF_DUAL_AS");
-        if (g) d.dual_as = atoi(g);
-        const char* l = getenv("MPCCBF_LEAN");
-        if (l) d.lean = atoi(l);
-        const char* w = getenv("MPCCBF_DAS_WARM");
-        if (w) d.das_warm = atoi(w);
-        const char* wd = getenv("MPCCBF_WARM_DELTA");
-        if (wd) d.warm_delta = std::max(0.0, std::strtod(wd, nullptr));
-    }
-#endif
+    const PackedOps packed = pack_operators(c->ops, *p, c->opt);
+    c->dev = packed.dev;
+    c->o_EB2 = packed.o_EB2;
     c->variant = 0;
     hipError_t e = hipSetDevice(c->device);
-    d.wide_max = 1024;
+    c->dev.wide_max = 1024;
     if (e == hipSuccess) {
         // share-adaptive layout: one agent per wave up to one agent per SIMD (4 per CU) of this
         // context's device (kept in the context: no process-wide state shared by contexts)
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
-            d.wide_max = 4 * prop.multiProcessorCount;
+            c->dev.wide_max = 4 * prop.multiProcessorCount;
     }
-    if (e == hipSuccess) e = hipMalloc(&c->dbuf, v.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(c->dbuf, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice);
+    const size_t bytes = packed.buf.size() * sizeof(double);
+    if (e == hipSuccess) e = c->dbuf.reserve(bytes);
+    if (e == hipSuccess) e = hipMemcpy(c->dbuf.p, packed.buf.data(), bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        if (c->dbuf) (void)hipFree(c->dbuf);
         delete c;
         return fail(MPCCBF_ERR_HIP, std::string("operator upload: ") + hipGetErrorString(e));
     }
-    c->dbuf_elems = v.size();
     *out = c;
     return MPCCBF_OK;
 }
@@ -665,13 +416,7 @@ int mpccbf_create(const mpccbf_params* p, const mpccbf_options* opt, mpccbf_ctx*
 void mpccbf_destroy(mpccbf_ctx* c) {
     if (!c) return;
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    if (c->dbuf) (void)hipFree(c->dbuf);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->grid_scratch) (void)hipFree(c->grid_scratch);
-    if (c->defer) (void)hipFree(c->defer);
-    if (c->audit_scratch) (void)hipFree(c->audit_scratch);
-    conn_free(c);
-    delete c;
+    delete c;  // (its device buffers with it)
 }
 
 int mpccbf_num_vars(const mpccbf_ctx* c) { return c ? c->ops.n : -1; }
@@ -679,21 +424,17 @@ int mpccbf_reduced_dim(const mpccbf_ctx* c) { return c ? c->ops.nz : -1; }
 int mpccbf_num_shared_rows(const mpccbf_ctx* c) { return c ? c->ops.G.r : -1; }
 
 int mpccbf_impc_solve(mpccbf_ctx* c, const mpccbf_batch* b, void* stream) {
-    return impc_enqueue(c, b, (hipStream_t)stream, nullptr, nullptr);
+    if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    return impc_enqueue(c, b, (hipStream_t)stream, nullptr, nullptr, c->dev, c->store);
 }
 
+// (neither the clock waves nor the name depend on where the neighbour lists come from)
 int32_t mpccbf_impc_launch_waves(const mpccbf_ctx* c, int32_t num_agents) {
-    if (!c) return 0;
-    if (c->conn.on) return impc_conn_clock_waves(num_agents);
-    return impc_clock_waves(launch_ops(c), c->variant, num_agents);
+    return c ? ctx_plan(c, num_agents, false, 0, c->store != nullptr).clock_waves : 0;
 }
 
 const char* mpccbf_kernel_name(const mpccbf_ctx* c) {
-    if (!c) return "";
-    if (c->conn.on) return impc_conn_kernel_name();
-    if (c->dev.cbf_mode == 1) return c->dev.slack_mode ? "impc_fov_kernel<true>" : "impc_fov_kernel<false>";
-    const char* n = impc_kernel_name(launch_ops(c), c->variant, c->last_n, c->store != nullptr);
-    return n ? n : "";
+    return c ? ctx_plan(c, c->last_n, false, 0, c->store != nullptr).name : "";
 }
 
 int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t min_steps) {
@@ -735,7 +476,7 @@ int mpccbf_set_connectivity(mpccbf_ctx* c, const mpccbf_connectivity* k) {
     if (c->dev.slack_mode) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: slack mode is not supported");
     if (c->dev.cbf_mode == 1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: the FoV controller is not supported");
     if (!(k->d_max > c->p.d_min)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: d_max must exceed d_min");
-    if (!impc_conn_ok(c->dev))
+    if (impc_launch_plan(c->dev, c->variant, 1, false, 0, false, true).kernel != IMPC_CONN)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: the separable collision controller only");
     (void)hipSetDevice(c->device);
     conn_free(c);
@@ -768,12 +509,9 @@ int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: not supported while connectivity is attached");
     if (c->dev.slack_mode) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: slack mode is not supported");
     if (c->dev.cbf_mode == 1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the FoV controller is not supported");
-    {
-        DevOps full = c->dev;
-        full.lean = 0;
-        if (!impc_store_ok(full, c->variant, b->num_agents > 0 ? b->num_agents : 1))
-            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the separable layouts only (variants 0, 4, 5)");
-    }
+    // (the layouts whose launches can take a store: the separable ones)
+    if (!ctx_plan(c, b->num_agents > 0 ? b->num_agents : 1, !grid, b->knn_k, true).store)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: the separable layouts only (variants 0, 4, 5)");
     if (c->p.impc_iter > 2) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "cap audit: impc_iter > 2 is not supported");
     if (b->num_agents == 0) return MPCCBF_OK;
     if (!b->states || (!grid && !b->nb_col && b->num_states > 1))
@@ -785,15 +523,9 @@ int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_
     HIP_TRY(hipSetDevice(c->device));
     const size_t xbytes = (size_t)b->num_agents * c->ops.n * sizeof(double);
     const size_t need = xbytes + (size_t)b->num_agents * sizeof(int32_t);
-    if (need > c->audit_bytes) {
-        if (c->audit_scratch) (void)hipFree(c->audit_scratch);
-        c->audit_scratch = nullptr;
-        c->audit_bytes = 0;
-        HIP_TRY(hipMalloc(&c->audit_scratch, need));
-        c->audit_bytes = need;
-    }
-    double* x0 = (double*)c->audit_scratch;
-    int32_t* st0 = (int32_t*)((char*)c->audit_scratch + xbytes);
+    HIP_TRY(c->audit_scratch.reserve(need));
+    double* x0 = c->audit_scratch.as<double>();
+    int32_t* st0 = (int32_t*)(c->audit_scratch.as<char>() + xbytes);
     // iteration 0's solutions: the context's own IMPC launch once more on the same batch with one
     // iteration, every output into scratch, no closed-loop state, no diagnostics, no active store
     // (grid mode: gstep < 0 rebuilds the table from b->states, so the lists are the solve's)
@@ -810,13 +542,9 @@ int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_
         sb.primal_res = sb.dual_res = nullptr;
         sb.substeps = nullptr;
         sb.nb_out = nullptr;
-        const int32_t iters = c->dev.impc_iter;
-        int32_t* const store = c->store;
-        c->dev.impc_iter = 1;
-        c->store = nullptr;
-        const int rc = impc_enqueue(c, &sb, stream, nullptr, nullptr);
-        c->dev.impc_iter = iters;
-        c->store = store;
+        DevOps one = c->dev;
+        one.impc_iter = 1;
+        const int rc = impc_enqueue(c, &sb, stream, nullptr, nullptr, one, nullptr);
         if (rc != MPCCBF_OK) return rc;
     }
     AuditArgs a;
@@ -838,7 +566,7 @@ int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_
     a.counts = au->counts;
     a.excess = au->excess;
     a.live_nb = au->live_nb;
-    HIP_TRY(launch_cap_audit(c->dev, c->dbuf, a, stream));
+    HIP_TRY(launch_cap_audit(c->dev, c->dbuf.as<double>(), a, stream));
     if (au->x0_out) HIP_TRY(hipMemcpyAsync(au->x0_out, x0, xbytes, hipMemcpyDeviceToDevice, stream));
     return MPCCBF_OK;
 }
@@ -859,15 +587,9 @@ int mpccbf_build_neighbors(mpccbf_ctx* c, const double* states, int32_t num_stat
     if (k > 0 && !(radius > 0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "radius must be positive");
     HIP_TRY(hipSetDevice(c->device));
     const size_t need = neighbors_scratch_bytes(num_states, num_agents, k);
-    if (need > c->scratch_bytes) {
-        if (c->scratch) (void)hipFree(c->scratch);
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&c->scratch, need));
-        c->scratch_bytes = need;
-    }
+    HIP_TRY(c->scratch.reserve(need));
     const int rc = launch_neighbors(states, num_states, first, num_agents, k, radius, row_ptr, col,
-                                    c->scratch, c->scratch_bytes, (hipStream_t)stream);
+                                    c->scratch.p, c->scratch.bytes, (hipStream_t)stream);
     if (rc != 0) return fail(MPCCBF_ERR_HIP, std::string("neighbour kernels: ") + hipGetErrorString((hipError_t)rc));
     return MPCCBF_OK;
 }
@@ -1097,7 +819,7 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
         }
         const bool tk = r->solve_ms && (r->solve_stride <= 1 || s % r->solve_stride == 0);
         const int rc = impc_enqueue(c, &sb, stream, tk ? ev[3 * s + 1] : nullptr, tk ? ev[3 * s + 2] : nullptr,
-                                    gtab ? gbase + s : -1,
+                                    c->dev, c->store, gtab ? gbase + s : -1,
                                     r->kernel_clock ? (unsigned long long*)r->kernel_clock +
                                                           2 * (size_t)r->kernel_clock_waves * s
                                                     : nullptr);

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../../include/mpccbf.h"
+#include "errors.hpp"
 #include "operators.hpp"
 
 using namespace mpccbf;
@@ -19,6 +20,11 @@ void put(const std::vector<double>& m, double* dst) {
     if (dst) std::memcpy(dst, m.data(), m.size() * sizeof(double));
 }
 }  // namespace
+
+int mpccbf::set_host_error(int code, const std::string& msg) {
+    g_diag_err = msg;
+    return code;
+}
 
 extern "C" {
 

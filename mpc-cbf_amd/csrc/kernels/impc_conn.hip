@@ -63,28 +63,11 @@ hipError_t launch_team_spectrum(const SpectrumArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// CBF row slots per lane of the connectivity launch: a full team of 16 at cbf_horizon 2 has 30
-// safety and 30 CLF rows
-constexpr int CONN_CB = 4, CONN_BS = 64;
-
-// Whether the connectivity launch applies: the separable collision controller without slack
-// variables, up to 16 box rows per channel
-bool impc_conn_ok(const DevOps& op) {
-    return op.cbf_mode == 0 && !op.slack_mode && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16;
-}
-
-const char* impc_conn_kernel_name() { return "impc_sep_conn_kernel<4,64>"; }
-
-// Waves of the connectivity launch that write the launch clock (one per 64-thread block)
-int impc_conn_clock_waves(int n) { return n <= 0 ? 0 : (n + CONN_BS / 16 - 1) / (CONN_BS / 16); }
-
-hipError_t launch_impc_conn(const DevOps& op, const double* buf, const ImpcArgs& a, const ConnArgs& cn, hipStream_t s) {
-    if (a.num_agents <= 0) return hipSuccess;
-    if (!impc_conn_ok(op)) return hipErrorInvalidValue;
-    constexpr int GPB = CONN_BS / 16;
-    const int blocks = (a.num_agents + GPB - 1) / GPB;
-    hipLaunchKernelGGL((dev::impc_sep_conn_kernel<CONN_CB, CONN_BS>), dim3(blocks), dim3(CONN_BS), 0, s, op, buf, a, cn);
-    return hipGetLastError();
+// (4 CBF row slots per lane: a full team of 16 at cbf_horizon 2 has 30 safety and 30 CLF rows)
+hipError_t launch_impc_conn(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
+                            const ImpcArgs& a, const ConnArgs& cn, hipStream_t s) {
+    if (k != IMPC_CONN) return hipErrorInvalidValue;
+    return launch_kernel(dev::impc_sep_conn_kernel<4, 64>, blocks, block_size, 0, s, op, buf, a, cn);
 }
 
 }  // namespace mpccbf

@@ -17,6 +17,7 @@
 #include "impc_common.hpp"
 #include "fov_cbf.hpp"
 #include "das_wave.hpp"
+#include "launch_plan.hpp"
 
 namespace mpccbf {
 namespace dev {
@@ -841,16 +842,15 @@ hipError_t launch_fov_rows_eval(int count, const double* ego, const double* nb, 
     return hipGetLastError();
 }
 
-hipError_t launch_impc_fov(const DevOps& op, const double* buf, const ImpcArgs& a, hipStream_t s) {
-    if (a.num_agents <= 0) return hipSuccess;
-    if (op.nz != 15 || op.m > dev::WROWS) return hipErrorInvalidValue;
-    if (op.slack_mode) {
-        if (op.cbf_h > 2) return hipErrorInvalidValue;  // 4 kinds x cbf_h rows per 8-lane segment
-        hipLaunchKernelGGL(dev::impc_fov_kernel<true>, dim3(a.num_agents), dim3(64), 0, s, op, buf, a);
-    } else {
-        hipLaunchKernelGGL(dev::impc_fov_kernel<false>, dim3(a.num_agents), dim3(64), 0, s, op, buf, a);
+const int IMPC_FOV_ROWS_MAX = dev::WROWS;
+
+hipError_t launch_impc_fov(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
+                           const ImpcArgs& a, hipStream_t s) {
+    switch (k) {  // (<true> first, as the instantiations have always stood: impc_kernel.hip's launch_impc)
+        case IMPC_FOV_SLACK: return launch_kernel(dev::impc_fov_kernel<true>, blocks, block_size, 0, s, op, buf, a);
+        case IMPC_FOV: return launch_kernel(dev::impc_fov_kernel<false>, blocks, block_size, 0, s, op, buf, a);
+        default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace mpccbf

@@ -30,6 +30,7 @@
 #include "pdip.hpp"
 #include "pdip_sep.hpp"
 #include "conn_rows.hpp"
+#include "launch_plan.hpp"
 
 namespace mpccbf {
 namespace dev {
@@ -1399,203 +1400,74 @@ __global__ void __launch_bounds__(BS) WIDE_WPE_ATTR impc_wide_store_kernel(const
 
 }  // namespace dev
 
-// The store kernels are instantiated in a translation unit of their own (impc_store.hip, which
-// defines MPCCBF_STORE_TU and includes this file): compiled next to them, the kernels launched
-// without a store came out of the compiler with other operand orders and a few bytes longer
-// (DESIGN.md section 4). launch_impc_store: which = STORE_WIDE / STORE_SEP (main launches),
-// STORE_QUEUE1 / STORE_QUEUE8 (capacity launch with 1 / 8 CBF slots per lane).
-enum { STORE_WIDE = 0, STORE_SEP = 1, STORE_QUEUE1 = 2, STORE_QUEUE8 = 3 };
-hipError_t launch_impc_store(const DevOps& op, const double* buf, const ImpcArgs& a, const StoreArgs& st, int which,
-                             hipStream_t s);
 
+// The launchers (launch_plan.hpp): a switch from the plan's kernel id to the instantiation, grid
+// and block as the plan gives them; which kernel runs when is impc_launch_plan's alone.
+// The store and connectivity kernels are instantiated in translation units of their own
+// (impc_store.hip / impc_conn.hip, which define MPCCBF_STORE_TU / MPCCBF_CONN_TU and include this
+// file): compiled next to them, the kernels launched without a store came out of the compiler with
+// other operand orders and a few bytes longer.
 #ifdef MPCCBF_STORE_TU
-template <int CB, int BS, bool QUEUE>
-static hipError_t launch_impc_sep_store_t(const DevOps& op, const double* buf, const ImpcArgs& a, const StoreArgs& st,
-                                          hipStream_t s) {
-    constexpr int GPB = BS / 16;
-    const int blocks = (a.num_agents + GPB - 1) / GPB;
-    hipLaunchKernelGGL((dev::impc_sep_store_kernel<CB, BS, QUEUE>), dim3(blocks), dim3(BS), 0, s, op, buf, a, st);
-    return hipGetLastError();
-}
-
-hipError_t launch_impc_store(const DevOps& op, const double* buf, const ImpcArgs& a, const StoreArgs& st, int which,
-                             hipStream_t s) {
-    if (which == STORE_SEP) return launch_impc_sep_store_t<1, 256, false>(op, buf, a, st, s);
-    if (which == STORE_QUEUE1) return launch_impc_sep_store_t<1, 64, true>(op, buf, a, st, s);
-    if (which == STORE_QUEUE8) return launch_impc_sep_store_t<8, 64, true>(op, buf, a, st, s);
-    constexpr int BS = 256, WPB = BS / 64;
-    const int blocks = (a.num_agents + WPB - 1) / WPB;
-    hipLaunchKernelGGL((dev::impc_wide_store_kernel<BS>), dim3(blocks), dim3(BS), 0, s, op, buf, a, st);
-    return hipGetLastError();
+hipError_t launch_impc_store(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
+                             const ImpcArgs& a, const StoreArgs& st, hipStream_t s) {
+    auto go = [&](auto kernel) { return launch_kernel(kernel, blocks, block_size, 0, s, op, buf, a, st); };
+    switch (k) {
+        case IMPC_SEP_STORE: return go(dev::impc_sep_store_kernel<1, 256, false>);
+        case IMPC_QUEUE1_STORE: return go(dev::impc_sep_store_kernel<1, 64, true>);
+        case IMPC_QUEUE8_STORE: return go(dev::impc_sep_store_kernel<8, 64, true>);
+        case IMPC_WIDE_STORE: return go(dev::impc_wide_store_kernel<256>);
+        default: return hipErrorInvalidValue;
+    }
 }
 #elif defined(MPCCBF_CONN_TU)
 // (impc_conn.hip: the connectivity launch and the per-team spectrum launch)
 #else
+const int IMPC_WIDE_OPS_MAX = dev::WIDE_OPS;
 
+// dense layout: the LDS row image of the agents of a block (G lanes per agent, R row slots per lane)
 template <int NZ, int G, int R>
-static hipError_t launch_impc_t(const DevOps& op, const double* buf, const ImpcArgs& a,
-                                hipStream_t s) {
-    constexpr int GPB = 256 / G;
-    const int blocks = (a.num_agents + GPB - 1) / GPB;
-    const size_t lds = (size_t)GPB * (R * G - op.m) * (NZ + 1) * sizeof(double);
-    hipLaunchKernelGGL((dev::impc_kernel<NZ, G, R>), dim3(blocks), dim3(256), lds, s, op, buf, a);
-    return hipGetLastError();
+static hipError_t launch_impc_dense(int blocks, int block_size, const DevOps& op, const double* buf,
+                                    const ImpcArgs& a, hipStream_t s) {
+    const size_t lds = (size_t)(block_size / G) * (R * G - op.m) * (NZ + 1) * sizeof(double);
+    return launch_kernel(dev::impc_kernel<NZ, G, R>, blocks, block_size, lds, s, op, buf, a);
 }
 
-template <int SB, int CB, bool SLACK, int BS = 256, bool QUEUE = false, bool LEAN = false>
-static hipError_t launch_impc_sep_t(const DevOps& op, const double* buf, const ImpcArgs& a,
-                                    hipStream_t s) {
-    constexpr int GPB = BS / 16;
-    int blocks = (a.num_agents + GPB - 1) / GPB;
-    hipLaunchKernelGGL((dev::impc_sep_kernel<SB, CB, SLACK, BS, QUEUE, LEAN>), dim3(blocks), dim3(BS), 0, s, op, buf,
-                       a);
-    return hipGetLastError();
-}
-
-// Whether the one-agent-per-wave kernel applies: the separable collision controller (no slack
-// variables) with the dual active set on; CBF samples <= MAX_CBF_H.
-static bool impc_wide_ok(const DevOps& op) {
-    return op.cbf_mode == 0 && !op.slack_mode && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16 &&
-           op.dual_as > 0 && op.cbf_h <= MAX_CBF_H && op.hot > 0 && op.hot <= dev::WIDE_OPS;
-}
-
-static hipError_t launch_impc_wide(const DevOps& op, const double* buf, const ImpcArgs& a, hipStream_t s) {
-    constexpr int BS = 256, WPB = BS / 64;
-    const int blocks = (a.num_agents + WPB - 1) / WPB;
-    hipLaunchKernelGGL((dev::impc_wide_kernel<BS>), dim3(blocks), dim3(BS), 0, s, op, buf, a);
-    return hipGetLastError();
-}
-
-// Layouts of the separable collision controller (mpccbf_set_variant):
+// Layouts of the separable collision controller (mpccbf_set_variant, impc_launch_plan):
 //   0 (default) — share-adaptive: up to one agent per SIMD of the device (1,024 on MI355X: config
 //       4's rank share) the one-agent-per-wave kernel (its fallback as a second launch); beyond,
 //       the 16-lane kernel (4 agents per wave: one wave per SIMD covers 4 x as many agents);
-//   VARIANT_SEP16 — the 16-lane kernel at any count (the layout of rounds 1-4);
-//   VARIANT_WIDE — the one-agent-per-wave kernel at any count.
+//   4 — the 16-lane kernel at any count (the layout of rounds 1-4);
+//   5 — the one-agent-per-wave kernel at any count.
 // (Round 6, measured and dropped: a lean-then-full variant — the fast start and the dual active
 // set, the full pipeline in place after the IMPC loop for the agents they do not settle — ran the
 // lean part 1.6 us slower than the lean kernel alone and 0.5 us slower than the full kernel.)
-constexpr int VARIANT_SEP16 = 4, VARIANT_WIDE = 5;
-static bool sep_variant(int variant) { return variant == 0 || variant == VARIANT_SEP16; }
-static bool use_wide(const DevOps& op, int variant, int n) {
-    return impc_wide_ok(op) && (variant == VARIANT_WIDE || (variant == 0 && n <= op.wide_max));
-}
-
-// Row slots per lane and channel of the separable slack kernel (1: up to 16 box rows per channel,
-// 2: up to 32, e.g. K = 16 as in the reference's instance files); 0: no slack instantiation fits
-static int slack_sb(const DevOps& op) {
-    if (!(op.sep && op.nzd == SEP_NZD_HOST && op.cbf_h <= 2)) return 0;
-    return op.sep_rows_per_dim <= 16 ? 1 : (op.sep_rows_per_dim <= 32 ? 2 : 0);
-}
-
-// The separable layout's lean main launch (fast start + dual active set; everything else deferred)
-static bool sep_lean(const DevOps& op, int variant, int n) {
-    return sep_variant(variant) && !use_wide(op, variant, n) && !op.slack_mode && op.sep && op.nzd == SEP_NZD_HOST &&
-           op.sep_rows_per_dim <= 16 && op.lean && op.dual_as > 0;
-}
-
-// Agents the main launch deferred are solved by this launch (the queue in a.queue):
+// Capacity launches (IMPC_QUEUE*): the agents the main launch deferred (the queue in a.queue):
 //   slack mode, more than 16 neighbours — the slack solver, the neighbours with a live row
 //   compacted into the lanes;
 //   otherwise — the full separable pipeline (dual active set, PDIP attempts, phase 1): with 16 CBF
 //   row slots when no agent can exceed them, else 8 slots per lane (128 rows). Agents beyond
 //   that report ERROR.
-hipError_t launch_impc_fallback(const DevOps& op, const double* buf, const ImpcArgs& a, bool wide,
-                                hipStream_t s, const StoreArgs& st) {
-    if (a.num_agents <= 0 || !a.queue) return hipSuccess;
-    if (op.slack_mode) {
-        if (slack_sb(op) == 2) return launch_impc_sep_t<2, 2, true, 64, true>(op, buf, a, s);
-        return launch_impc_sep_t<1, 2, true, 64, true>(op, buf, a, s);
-    }
-    // (a store is attached: the store instantiations, as the main launch's)
-    if (st.records != nullptr) return launch_impc_store(op, buf, a, st, wide ? STORE_QUEUE8 : STORE_QUEUE1, s);
-    if (wide) return launch_impc_sep_t<1, 8, false, 64, true>(op, buf, a, s);
-    return launch_impc_sep_t<1, 1, false, 64, true>(op, buf, a, s);
-}
-
-// Whether the launch for (operators, variant, agents) reads and writes the active-set store: the
-// separable collision controller without slack variables, 16-lane full kernel or wide kernel, and
-// their capacity launch. (The lean main launch has no store instantiation: the caller clears
-// DevOps::lean while a store is attached.)
-bool impc_store_ok(const DevOps& op, int variant, int n) {
-    if (op.cbf_mode != 0 || op.slack_mode || sep_lean(op, variant, n)) return false;
-    if (use_wide(op, variant, n)) return true;
-    return sep_variant(variant) && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16;
-}
-
-// Whether some agent can exceed the default separable kernel's 16 CBF row slots (caller lists,
-// or k nearest x CBF samples > 16).
-bool impc_rows_may_exceed(const DevOps& op, bool csr, int knn_k) { return csr || knn_k * op.cbf_h > 16; }
-
-// Whether launch_impc defers agents (so launch_impc_fallback must follow): the lean main launches
-// always may; the full separable kernel and the wide kernel with the inline fallback when their 16
-// CBF row slots can be exceeded.
-bool impc_may_defer(const DevOps& op, int variant, bool csr, int knn_k, int n) {
-    // slack mode: more than 16 neighbours only from caller lists (grid mode takes knn_k <= 16,
-    // impc_enqueue)
-    if (op.slack_mode) return slack_sb(op) > 0 && csr;
-    if (use_wide(op, variant, n) || sep_lean(op, variant, n)) return true;
-    if (!(sep_variant(variant) && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16)) return false;
-    return impc_rows_may_exceed(op, csr, knn_k);
-}
-
-// Waves of the main IMPC launch for n agents that write the launch clock (ImpcArgs::kclock: the
-// separable and wide collision kernels; 0 for the others)
-int impc_clock_waves(const DevOps& op, int variant, int n) {
-    if (n <= 0 || op.cbf_mode != 0) return 0;
-    if (use_wide(op, variant, n)) return ((n + 3) / 4) * 4;  // 256-thread blocks, one agent per wave
-    const bool sep = op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16;
-    if (op.slack_mode && slack_sb(op) == 2) return ((n + 7) / 8) * 2;  // 128-thread blocks of 8 groups
-    if (op.slack_mode ? slack_sb(op) > 0 : (sep && sep_variant(variant)))
-        return ((n + 15) / 16) * 4;  // 256-thread blocks of 16 groups
-    return 0;
-}
-
-// Instantiation launch_impc picks for (operators, variant, agents per launch); nullptr if none fits.
-const char* impc_kernel_name(const DevOps& op, int variant, int n, bool store) {
-    if (store && impc_store_ok(op, variant, n))
-        return use_wide(op, variant, n) ? "impc_wide_store_kernel<256>" : "impc_sep_store_kernel<1,256,false>";
-    if (op.slack_mode) {  // slack variables: separable layout, one lane per neighbour, cbf_h <= 2
-        const int sb = slack_sb(op);
-        return sb == 1 ? "impc_sep_kernel<1,2,true,256>" : (sb == 2 ? "impc_sep_kernel<2,2,true,128>" : nullptr);
-    }
-    if (use_wide(op, variant, n)) return "impc_wide_kernel<256>";
-    if (sep_lean(op, variant, n)) return "impc_sep_kernel<1,1,false,256,false,true>";
-    if (sep_variant(variant) && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16)
-        return "impc_sep_kernel<1,1,false,256>";
-    if (op.nz == 6) {
-        if ((variant == 0 || variant == 3) && op.m < 64) return "impc_kernel<6,16,4>";
-        if (variant == 1 && op.m < 64) return "impc_kernel<6,64,1>";
-        if (op.m < 256) return "impc_kernel<6,64,4>";
-    }
-    return nullptr;
-}
-
-// st.records: set by the caller only where impc_store_ok
-hipError_t launch_impc(const DevOps& op, const double* buf, const ImpcArgs& a, int variant,
-                       hipStream_t s, const StoreArgs& st) {
-    if (a.num_agents <= 0) return hipSuccess;
-    if (op.slack_mode) {
-        const int sb = slack_sb(op);
-        if (sb == 1) return launch_impc_sep_t<1, 2, true>(op, buf, a, s);
+hipError_t launch_impc(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
+                       const ImpcArgs& a, hipStream_t s) {
+    auto go = [&](auto kernel) { return launch_kernel(kernel, blocks, block_size, 0, s, op, buf, a); };
+    // (the cases in the order the instantiations have always had in this file: the compiler lays
+    // the kernels out in it, and tools/code_sizes.py's hashes see a kernel's distance to its data)
+    switch (k) {
+        case IMPC_WIDE: return go(dev::impc_wide_kernel<256>);
+        case IMPC_QUEUE_SLACK2: return go(dev::impc_sep_kernel<2, 2, true, 64, true>);
+        case IMPC_QUEUE_SLACK1: return go(dev::impc_sep_kernel<1, 2, true, 64, true>);
+        case IMPC_QUEUE8: return go(dev::impc_sep_kernel<1, 8, false, 64, true>);
+        case IMPC_QUEUE1: return go(dev::impc_sep_kernel<1, 1, false, 64, true>);
+        case IMPC_SLACK1: return go(dev::impc_sep_kernel<1, 2, true, 256>);
         // (two box slots per lane: 128-thread blocks, the 256-thread block's LDS is past 160 KB)
-        if (sb == 2) return launch_impc_sep_t<2, 2, true, 128>(op, buf, a, s);
-        return hipErrorInvalidValue;
+        case IMPC_SLACK2: return go(dev::impc_sep_kernel<2, 2, true, 128>);
+        case IMPC_SEP_LEAN: return go(dev::impc_sep_kernel<1, 1, false, 256, false, true>);
+        case IMPC_SEP: return go(dev::impc_sep_kernel<1, 1, false, 256>);
+        case IMPC_DENSE_16_4: return launch_impc_dense<6, 16, 4>(blocks, block_size, op, buf, a, s);
+        case IMPC_DENSE_64_1: return launch_impc_dense<6, 64, 1>(blocks, block_size, op, buf, a, s);
+        case IMPC_DENSE_64_4: return launch_impc_dense<6, 64, 4>(blocks, block_size, op, buf, a, s);
+        default: return hipErrorInvalidValue;
     }
-    const bool store = st.records != nullptr;
-    if (use_wide(op, variant, a.num_agents))
-        return store ? launch_impc_store(op, buf, a, st, STORE_WIDE, s) : launch_impc_wide(op, buf, a, s);
-    if (sep_lean(op, variant, a.num_agents)) return launch_impc_sep_t<1, 1, false, 256, false, true>(op, buf, a, s);
-    if (sep_variant(variant) && op.sep && op.nzd == SEP_NZD_HOST && op.sep_rows_per_dim <= 16) {
-        if (store) return launch_impc_store(op, buf, a, st, STORE_SEP, s);
-        return launch_impc_sep_t<1, 1, false>(op, buf, a, s);
-    }
-    if (op.nz == 6) {
-        if ((variant == 0 || variant == 3) && op.m < 64) return launch_impc_t<6, 16, 4>(op, buf, a, s);
-        if (variant == 1 && op.m < 64) return launch_impc_t<6, 64, 1>(op, buf, a, s);
-        if (op.m < 256) return launch_impc_t<6, 64, 4>(op, buf, a, s);
-    }
-    return hipErrorInvalidValue;
 }
 #endif  // MPCCBF_STORE_TU
 

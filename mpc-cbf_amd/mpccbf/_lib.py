@@ -24,6 +24,7 @@ EXPORTED = [
     "mpccbf_connectivity_control_solve", "mpccbf_host_operators", "mpccbf_host_last_error",
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
     "mpccbf_set_active_store", "mpccbf_cap_audit_run", "mpccbf_set_connectivity",
+    "mpccbf_host_launch_plan",
 ]
 
 # active-set store (mpccbf_set_active_store): int32 words per record, side keys per record
@@ -565,6 +566,43 @@ def host_operators(cfg: dict, keep_redundant: bool = False) -> dict:
         raise MpccbfError(L.mpccbf_host_last_error().decode())
     arrs.update(n=n, nz=nz, m=m, mc=mc, rows_total=o.rows_total, rows_removed=o.rows_removed)
     return arrs
+
+
+HOST_PLAN_OFFSETS = 38
+
+
+class HostPlan(C.Structure):
+    _fields_ = [("kernel_name", C.c_char_p), ("capacity_name", C.c_char_p)] + [
+        (f, C.c_int32) for f in ("block_size", "agents_per_block", "clock_waves", "store", "defers", "hot",
+                                 "total", "wide_capacity", "sep", "sep_rows_per_dim", "sep_sb", "o_Gsep")] + [
+        ("offsets", C.c_int32 * HOST_PLAN_OFFSETS), ("buf", C.c_void_p), ("buf_capacity", C.c_int32)]
+
+
+def host_launch_plan(cfg: dict, variant: int = 0, num_agents: int = 0, csr: bool = False, knn_k: int = 0,
+                     store: bool = False, connectivity: bool = False, wide_max: int = 1024,
+                     with_buffer: bool = False, **options) -> dict:
+    """Host-only launch plan and operator packing (mpccbf_host_launch_plan); no GPU needed.
+    options: fields of mpccbf_options (lean=1, keep_redundant=1, ...). Returns the fields of
+    mpccbf_host_plan as a dict (names decoded, offsets a list; buf: the packed operators as a numpy
+    array when with_buffer)."""
+    L = load()
+    L.mpccbf_host_launch_plan.argtypes = [C.POINTER(Params), C.POINTER(Options)] + [C.c_int32] * 7 + [
+        C.POINTER(HostPlan)]
+    L.mpccbf_host_last_error.restype = C.c_char_p
+    p, o, out = Params.from_dict(cfg), Options(**options), HostPlan()
+    args = (C.byref(p), C.byref(o), int(variant), int(num_agents), int(csr), int(knn_k), int(store),
+            int(connectivity), int(wide_max), C.byref(out))
+    buf = None
+    for _ in range(2 if with_buffer else 1):
+        if L.mpccbf_host_launch_plan(*args) != 0:
+            raise MpccbfError(L.mpccbf_host_last_error().decode())
+        if with_buffer and buf is None:
+            buf = np.zeros(out.total)
+            out.buf, out.buf_capacity = buf.ctypes.data, out.total
+    r = {f: getattr(out, f) for f, _ in HostPlan._fields_ if f not in ("offsets", "buf", "buf_capacity")}
+    r.update(kernel_name=out.kernel_name.decode(), capacity_name=out.capacity_name.decode(),
+             offsets=list(out.offsets), buf=buf)
+    return r
 
 
 def dense_qp_solve(H, c, A, lo, hi, vlo=None, vhi=None, c0=0.0):

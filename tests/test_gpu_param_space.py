@@ -229,7 +229,7 @@ def test_cbf_horizon_lattice_matches_oracle(mpclib, cbf_h):
 
 def test_cbf_horizon_3_grid_mode_equals_csr(mpclib):
     """Grid mode with 8 neighbours starts deferring at cbf_horizon = 3 (8 x 3 > 16 row slots,
-    impc_rows_may_exceed): the grid solve equals the CSR solve on the same lists."""
+    impc_launch_plan): the grid solve equals the CSR solve on the same lists."""
     torch = _torch()
     st, tg, rp, col = lattice()
     cfg = swarm.config(15, cbf_horizon=3)

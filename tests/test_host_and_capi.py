@@ -42,7 +42,7 @@ def test_abi_version_and_status_strings(mpclib):
 
 def test_release_library_reads_no_solver_env_vars(mpclib):
     """Solver decisions come from mpccbf_options alone: the release library does not even name the
-    diagnostics build's tuning variables (capi.hip, MPCCBF_DIAG_ENV); no getenv call site is
+    diagnostics build's tuning variables (launch_plan.hip, MPCCBF_DIAG_ENV); no getenv call site is
     compiled in (the GPU-side check: test_gpu_parity.py::test_solver_env_vars_have_no_effect)."""
     blob = open(mpclib.LIB_PATH, "rb").read()
     for name in (b"MPCCBF_DUAL_AS", b"MPCCBF_EARLY_IT", b"MPCCBF_FAST_START", b"MPCCBF_LEAN",

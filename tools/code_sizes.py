@@ -20,7 +20,7 @@ LLVM = "/opt/rocm/llvm/bin"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
          "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 SRCS = ["csrc/kernels/impc_kernel.hip", "csrc/kernels/impc_store.hip", "csrc/kernels/impc_conn.hip",
-        "csrc/kernels/connectivity_control.hip"]
+        "csrc/kernels/impc_fov.hip", "csrc/kernels/connectivity_control.hip"]
 
 
 def device_code(src):
@@ -52,6 +52,8 @@ def main():
         if m:
             cur = m.group(1)
             body[cur] = []
+        elif "file format" in ln or ln.startswith("Disassembly of section"):
+            cur = None  # (the next object's header, with its temporary path: no kernel's instructions)
         elif cur is not None and ln.strip():
             body[cur].append(re.sub(r"\s*//.*$", "", ln.strip()))
     names = sorted(sizes)

@@ -25,22 +25,9 @@ constexpr int AS_KEYS = 5;                   // side keys a record holds (DK of 
 constexpr int AS_BOX_KEYS = 2 * SEP_D * 16;  // box keys are 0 .. AS_BOX_KEYS - 1
 static_assert(DK <= AS_KEYS, "a record holds the 16-lane solver's whole active set");
 
-// neighbour and sample of a CBF key (key < 0; INT_MIN included: no overflow)
+// neighbour of a CBF key (key < 0; INT_MIN included: no overflow). Every sample of the neighbour
+// maps: an A/B build measured same-sample-only and next-sample-only keys
 __device__ __forceinline__ int as_key_nb(int key) { return (int)((unsigned)(-(key + 1)) >> 3); }
-__device__ __forceinline__ int as_key_sample(int key) { return (-(key + 1)) & 7; }
-
-// Which CBF keys of the record start iteration 0's solve (A/B builds of DESIGN.md section 4's
-// mapping rows: `make relv V=MAPS0` / `make relv V=MAPS1` -> build/rel_MAPS*/libmpccbf.so, chosen
-// with MPCCBF_LIB; the default takes every sample of the neighbour)
-__device__ __forceinline__ bool as_sample_maps(int sample) {
-#if defined(MPCCBF_V_MAPS0)  // the same sample only
-    return sample == 0;
-#elif defined(MPCCBF_V_MAPS1)  // the next sample only (step t's sample 1 is step t + 1's state)
-    return sample == 1;
-#else
-    return true;
-#endif
-}
 
 // The record's keys as side ids of the 16-lane layout (pdip_sep.hpp POL_ID: side * 16 + lane; box
 // side 2 d + upper of lane = row, CBF slot c of lane l = staged row c * 16 + l) into ids[0 .. n);
@@ -63,7 +50,7 @@ __device__ __forceinline__ int as_map_sep(lds_vptr<int32_t> rec, lds_vptr<int32_
         if (key >= 0) {
             const int row = (key >> 1) & 15;
             if (key < AS_BOX_KEYS && row < rows_per_dim) id = (2 * (key >> 5) + (key & 1)) * 16 + row;
-        } else if (as_sample_maps(as_key_sample(key))) {
+        } else {  // (a CBF key: every sample of the neighbour maps)
             const int nb = as_key_nb(key);
 #pragma unroll
             for (int c = 0; c < CB; c++) {
@@ -118,7 +105,7 @@ __device__ __forceinline__ int as_map_wide(lds_vptr<int32_t> rec, lds_vptr<int32
         int id = -1;
         if (key >= 0) {
             if (key < AS_BOX_KEYS && ((key >> 1) & 15) < rows_per_dim) id = key;
-        } else if (as_sample_maps(as_key_sample(key))) {
+        } else {  // (a CBF key: every sample of the neighbour maps)
             const int nb = as_key_nb(key);
             const bool hit = gl < live && as_key_nb(tags[gl < live ? gl : 0]) == nb;
             const unsigned long long m = __ballot(hit);

@@ -1,7 +1,8 @@
 // conn_spectrum.hpp — a team's weighted Laplacian spectrum on one wavefront: lambda2 and the unit
 // Fiedler vector (ConnectivityCBF::getLambda2, ConnectivityCBF.cpp:368-414). Shared by the CBF-only
 // connectivity controller (connectivity_control.hip) and the per-team spectrum launch of the
-// batched IMPC's connectivity rows (impc_conn.hip).
+// batched IMPC's connectivity rows (team_spectrum_kernel, impc_conn.hip; the rows themselves:
+// conn_rows_dev.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

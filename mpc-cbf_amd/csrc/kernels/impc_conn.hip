@@ -1,12 +1,11 @@
 // impc_conn.hip — the batched IMPC with connectivity-maintenance rows (mpccbf_set_connectivity):
 // the per-team spectrum launch (team_spectrum_kernel) and the IMPC launch that stages the rows
-// (impc_sep_conn_kernel: impc_kernel.hip, conn_rows.hpp). A translation unit of its own, as
+// (impc_sep_conn_kernel: impc_sep.hpp, conn_rows_dev.hpp). A translation unit of its own, as
 // impc_store.hip, so that the object code of the kernels launched without connectivity does not
-// depend on it.
-#define MPCCBF_CONN_TU
-#include "impc_kernel.hip"
-
+// depend on it ("Why separate translation units").
+#include "impc_sep.hpp"
 #include "conn_spectrum.hpp"
+#include "launch_plan.hpp"
 
 namespace mpccbf {
 namespace dev {

@@ -538,10 +538,7 @@ __global__ void __launch_bounds__(64) impc_fov_kernel(const DevOps op, const dou
             // slack row (it leads its neighbour), else the certificate's active slack row of
             // largest weight whose neighbour has no leader. After SLK_PATTERNS patterns, or
             // when no rule applies, the slack PDIP solves.
-#ifndef MPCCBF_SLK_PATTERNS
-#define MPCCBF_SLK_PATTERNS 8
-#endif
-            constexpr int SLK_PATTERNS = MPCCBF_SLK_PATTERNS;
+            constexpr int SLK_PATTERNS = 8;
             bool lv = false, pattern_ok = false;
             int ncbf = 0, c_me = 0;
             if constexpr (SLACK) {
@@ -846,7 +843,7 @@ const int IMPC_FOV_ROWS_MAX = dev::WROWS;
 
 hipError_t launch_impc_fov(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
                            const ImpcArgs& a, hipStream_t s) {
-    switch (k) {  // (<true> first, as the instantiations have always stood: impc_kernel.hip's launch_impc)
+    switch (k) {  // (<true> first, as the instantiations have always stood: see launch_impc, impc_kernel.hip)
         case IMPC_FOV_SLACK: return launch_kernel(dev::impc_fov_kernel<true>, blocks, block_size, 0, s, op, buf, a);
         case IMPC_FOV: return launch_kernel(dev::impc_fov_kernel<false>, blocks, block_size, 0, s, op, buf, a);
         default: return hipErrorInvalidValue;

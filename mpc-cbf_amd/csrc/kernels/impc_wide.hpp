@@ -23,8 +23,8 @@
 // (impc_sep_kernel<.., QUEUE>: the full pipeline with the PDIP and phase 1), exactly as the lean
 // 16-lane launch did. So every status this kernel returns is either the active set's exact optimum,
 // a certified infeasibility, or the 16-lane pipeline's own result.
-// (Device code, included by impc_kernel.hip, which instantiates the kernels: the inline-fallback
-// form calls that file's 16-lane agent pipeline, impc_sep_agent.)
+// (Device code: the lane layout and the solver. The agent pipeline and the kernels on top of it
+// are impc_wide_kernels.hpp, instantiated by impc_kernel.hip and impc_store.hip.)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -17,23 +17,23 @@ struct AuditArgs;
 
 enum ImpcKernel : int32_t {
     IMPC_NONE = 0,     // no instantiation fits (the launch reports hipErrorInvalidValue)
-    IMPC_DENSE_16_4,   // impc_kernel<6,16,4>
+    IMPC_DENSE_16_4,   // impc_kernel.hip: impc_kernel<6,16,4> (impc_dense.hpp)
     IMPC_DENSE_64_1,   // impc_kernel<6,64,1>
     IMPC_DENSE_64_4,   // impc_kernel<6,64,4>
-    IMPC_SEP,          // impc_sep_kernel<1,1,false,256>
+    IMPC_SEP,          // impc_sep_kernel<1,1,false,256> (impc_sep.hpp)
     IMPC_SEP_LEAN,     // impc_sep_kernel<1,1,false,256,false,true>
     IMPC_SLACK1,       // impc_sep_kernel<1,2,true,256>
     IMPC_SLACK2,       // impc_sep_kernel<2,2,true,128>
-    IMPC_WIDE,         // impc_wide_kernel<256>
+    IMPC_WIDE,         // impc_wide_kernel<256> (impc_wide_kernels.hpp)
     IMPC_QUEUE1,       // capacity launches: impc_sep_kernel<1,1,false,64,true>
     IMPC_QUEUE8,       //   impc_sep_kernel<1,8,false,64,true>
     IMPC_QUEUE_SLACK1, //   impc_sep_kernel<1,2,true,64,true>
     IMPC_QUEUE_SLACK2, //   impc_sep_kernel<2,2,true,64,true>
-    IMPC_SEP_STORE,    // impc_store.hip: impc_sep_store_kernel<1,256,false>
-    IMPC_WIDE_STORE,   //   impc_wide_store_kernel<256>
+    IMPC_SEP_STORE,    // impc_store.hip: impc_sep_store_kernel<1,256,false> (impc_sep.hpp)
+    IMPC_WIDE_STORE,   //   impc_wide_store_kernel<256> (impc_wide_kernels.hpp)
     IMPC_QUEUE1_STORE, //   impc_sep_store_kernel<1,64,true>
     IMPC_QUEUE8_STORE, //   impc_sep_store_kernel<8,64,true>
-    IMPC_CONN,         // impc_conn.hip: impc_sep_conn_kernel<4,64>
+    IMPC_CONN,         // impc_conn.hip: impc_sep_conn_kernel<4,64> (impc_sep.hpp)
     IMPC_FOV,          // impc_fov.hip: impc_fov_kernel<false>
     IMPC_FOV_SLACK,    //   impc_fov_kernel<true>
 };

@@ -425,12 +425,10 @@ __device__ __forceinline__ void sep_gram(const double* __restrict__ pol, int k, 
 // sides is a valid start, so a side whose slot now holds another row only costs steps.
 // save: at convergence the final active set's side ids are written there (lane 0; their count
 // at save[POL_K]).
-// Active sides the dual active set's factor holds (L, multipliers, substitutions): DAS_K <= POL_K
-// (the staged-row layout); a QP that needs more gives up to the PDIP. (MPCCBF_DAS_K: A/B builds)
-#ifndef MPCCBF_DAS_K
-#define MPCCBF_DAS_K 5
-#endif
-constexpr int DK = MPCCBF_DAS_K;
+// Active sides the dual active set's factor holds (L, multipliers, substitutions): DK <= POL_K
+// (the staged-row layout); a QP that needs more gives up to the PDIP. Fixed: the warm start's
+// register arrays and the store's records (active_store.hpp AS_KEYS) are sized by it.
+constexpr int DK = 5;
 static_assert(DK >= 1 && DK <= POL_K, "the factor holds at most POL_K staged rows");
 template <int G, int SB, int CB>
 __device__ int sep_dual_as(const SepRows<SB, CB>& rw, bool has_cbf, const double* __restrict__ P,
@@ -570,7 +568,6 @@ __device__ int sep_dual_as(const SepRows<SB, CB>& rw, bool has_cbf, const double
         // ties): the side violated beyond the tolerance with the largest normalised violation. A
         // NaN row or iterate (a NaN state, target or neighbour state) shows as a NaN violation on
         // the first scan: give up, the caller's finiteness checks decide.
-#ifndef MPCCBF_SCAN_F64
         // keys: a violated side's normalised violation as a float bit pattern (at least 1: a score
         // that rounds to 0 in float still counts as violated), 0 for the others — the wide
         // kernel's rule (impc_wide.hpp): the group max is one u32 DPP reduction, the lane's best
@@ -624,52 +621,6 @@ __device__ int sep_dual_as(const SepRows<SB, CB>& rw, bool has_cbf, const double
         if (steps >= maxstep) return 0;
         if (kmax == 1u) return 0;  // the best score is 0 or denormal in float: no usable rule (PDIP)
         const int owner = __ffsll((long long)grp_ballot<G>(kb == kmax)) - 1;
-#else  // (A/B build: double scores, two interleaved max reductions)
-        double vb = -1.0, eb = -1.0;
-        int sb = 0;
-        bool nanv = false;
-        {
-            int s = 0, r = 0;
-#pragma unroll
-            for (int d = 0; d < SEP_D; d++)
-#pragma unroll
-                for (int kk = 0; kk < SB; kk++, r++) {
-                    const double t = rw.bg[d][kk][0] * y[2 * d] + rw.bg[d][kk][1] * y[2 * d + 1];
-                    const double w = (double)wbox[r * 16 + gl];
-                    const double al = rw.blo[d][kk] - t, vl = al * sc[s];
-                    const double el = vl > add_tol ? al * w : -1.0;
-                    if (el > eb) eb = el, sb = s;
-                    s++;
-                    const double au = t - rw.bhi[d][kk], vu = au * sc[s];
-                    const double eu = vu > add_tol ? au * w : -1.0;
-                    if (eu > eb) eb = eu, sb = s;
-                    s++;
-                    nanv = nanv || vl != vl || vu != vu;
-                    vb = fmax(vb, fmax(vl, vu));
-                }
-            if (has_cbf) {
-#pragma unroll
-                for (int c = 0; c < CB; c++, s++, r++) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 4; j++) t = fma(rw.cg[c][j], y[j], t);
-                    const double ac = t - rw.chi[c], vc = ac * sc[s];
-                    const double ec = vc > add_tol ? ac * (double)wrow[r * 16 + gl] : -1.0;
-                    if (ec > eb) eb = ec, sb = s;
-                    nanv = nanv || vc != vc;
-                    vb = fmax(vb, vc);
-                }
-            }
-        }
-        if (outer == 0 && grp_ballot<G>(nanv) != 0ull) return 0;
-        m = vb;
-        double em = eb;
-        grp_max2<G>(m, em);
-        GSTAMP(2 + 6 * outer, outer < 2);
-        if (!(m > add_tol)) break;
-        if (steps >= maxstep) return 0;
-        const int owner = __ffsll((long long)grp_ballot<G>(eb == em)) - 1;
-#endif
         if (gl == owner) sep_stage_side<SB, CB>(rw, pi, sb, gl, cand);
         wave_lds_sync();
         GSTAMP(3, outer == 0);
@@ -709,13 +660,9 @@ __device__ int sep_dual_as(const SepRows<SB, CB>& rw, bool has_cbf, const double
             const double sp = cand[POL_SGN];
             // rows at or beyond the wave's largest active count kw are identity rows of L with zero
             // right-hand side (v = rho = 0 there): skipped by scalar branches (kw is wave-uniform)
-#ifndef MPCCBF_NO_KW
             int kw = 0;
 #pragma unroll
             for (int i = 1; i <= DK; i++) kw += __ballot(k >= i) != 0ull ? 1 : 0;
-#else  // comparison build: every row
-            constexpr int kw = DK;
-#endif
             // v = L^-1 (sp c), c_i = g_i P^-1 g_p: the forward substitution fused with the dots
             double v[DK], sgn[DK];
 #pragma unroll

@@ -27,7 +27,7 @@ namespace mpccbf {
 namespace dev {
 
 // Accepted dual residual at primal convergence in slack mode: the recovered duals of strongly
-// active slack rows carry the rounding of the elimination (see pdip_wave.hpp MPCCBF_SLK_RD).
+// active slack rows carry the rounding of the elimination (see pdip_wave.hpp SLK_RD).
 constexpr double SLACK_LANE_RD_FLOOR = 1e-6;
 
 struct SlackLaneOut {

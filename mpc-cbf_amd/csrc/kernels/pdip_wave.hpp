@@ -136,12 +136,7 @@ struct WaveRows {
     double lo[WR], hi[WR], ml[WR];
 };
 
-#ifndef MPCCBF_SLK_RD  // slack mode: accepted dual-residual floor at primal convergence
-#define MPCCBF_SLK_RD 1e-6
-#endif
-#ifndef MPCCBF_SLK_INIT  // slack start: 1 = balanced (v = sb = 1/zb), 0 = v = sb = 1
-#define MPCCBF_SLK_INIT 1
-#endif
+constexpr double SLK_RD = 1e-6;  // slack mode: accepted dual-residual floor at primal convergence
 // ---- slack mode (FovBezierIMPCCBF slack_mode, FovMPCCBFQPGenerator.cpp:110-207) --------------
 // Neighbour i (< 8) owns a slack variable v_i >= 0 with linear cost w_i that relaxes all of its
 // FoV rows  g_a^T y - v_i <= h_a  (up to 8: 4 kinds x cbf_horizon <= 2). Lane l holds row a = l & 7
@@ -421,10 +416,8 @@ __device__ __forceinline__ PdipOut pdip_solve_wave(const WaveRows& rw, const dou
         sliv = son ? sk.live : 0.0;
         slw = son ? sk.w : 0.0;
         zb = fmax(slw, 1.0);
-#if MPCCBF_SLK_INIT == 1
-        sb = rcp(zb);  // balanced start: sb zb = 1
+        sb = rcp(zb);  // balanced start: v = sb = 1 / zb, so sb zb = 1
         v = sb;
-#endif
         const double t = son ? dotl(sk.Go + lane * WNZ, sc.y) : 0.0;
         cs = fmax(slh - (t - sliv * v), 1.0);
         cz = rcp(cs);
@@ -538,8 +531,8 @@ __device__ __forceinline__ PdipOut pdip_solve_wave(const WaveRows& rw, const dou
             // elimination (errors ~ eps D |dy| in dz of strongly active rows), which floors the
             // exact dual residual near 1e-8 .. 1e-7 once D ~ 1e13 while the primal iterate is
             // converged; with primal feasibility and complementarity at tolerance, a dual residual
-            // below MPCCBF_SLK_RD is accepted
-            if (rd_track <= cfg.tol || (SLK && rd_track <= MPCCBF_SLK_RD)) {
+            // below SLK_RD is accepted
+            if (rd_track <= cfg.tol || (SLK && rd_track <= SLK_RD)) {
                 out.status = ST_OPTIMAL;
                 out.rp = rp;
                 out.rd = rd_track;

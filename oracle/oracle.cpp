@@ -557,7 +557,7 @@ struct Assembler {
                 // v_i = 0 (b >= max over the box of -a^T u) holds for every v_i >= 0 too, and the
                 // box rows of sample k (addEvalBoundConstraints(2, ...), below) are in every QP —
                 // dropping it leaves the feasible set and the optimum unchanged (the kernel's
-                // filter, impc_kernel.hip lane_cbf_rows). Kept, a distant neighbour's row has a
+                // filter, impc_sep.hpp lane_cbf_rows). Kept, a distant neighbour's row has a
                 // bound ~1e26 next to a slack weight down to ~1e-9, and the dense PDIP stalls on
                 // its dual residual (round 3: two all-neighbour slack QPs UNKNOWN).
                 double bmax = 0.0;

@@ -1,5 +1,7 @@
 """Per-kernel code size and instruction hash of the IMPC kernels (cross-compile only, no GPU): the
-device code of csrc/kernels/impc_kernel.hip and impc_store.hip is compiled for gfx950 on its own
+device code of each translation unit that instantiates them (csrc/kernels/impc_kernel.hip, impc_store.hip,
+impc_conn.hip, impc_fov.hip; the kernels themselves are in the per-layout headers impc_dense.hpp,
+impc_sep.hpp, impc_wide_kernels.hpp) and of connectivity_control.hip is compiled for gfx950 on its own
 (--offload-device-only), and for every kernel symbol the table gives its size in bytes and the
 SHA-1 of its disassembled instructions (mnemonics and operands; addresses and encodings dropped).
 Two trees whose lines agree launch the same instructions for that kernel: the check that a change

@@ -5,7 +5,8 @@ a wait for it before the next load issues is a serialised round trip; scratch li
 
     python tools/isa_waits.py <src.hip> <kernel-name-substring> [max-lines] [-D...]
 e.g.  python tools/isa_waits.py csrc/kernels/impc_kernel.hip impc_sep_kernelILi1ELi1ELb0ELi256ELb0ELb0E
-(paths relative to mpc-cbf_amd/)"""
+(paths relative to mpc-cbf_amd/; <src.hip> is the translation unit that instantiates the kernel, whose
+source lines are in the per-layout headers: impc_dense.hpp, impc_sep.hpp, impc_wide_kernels.hpp)"""
 import os
 import re
 import subprocess

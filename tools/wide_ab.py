@@ -1,5 +1,5 @@
-"""A/B of the one-agent-per-wave kernel (variant 0, impc_wide.hip) against the 16-lane separable
-kernel (variant 4, impc_kernel.hip) on identical inputs: closed-loop-evolved state tables of the
+"""A/B of the one-agent-per-wave kernel (variant 0, impc_wide_kernels.hpp) against the 16-lane separable
+kernel (variant 4, impc_sep.hpp) on identical inputs: closed-loop-evolved state tables of the
 bench swarms, one mpccbf_impc_solve per table and variant. Prints per-table status agreement,
 objective / control-point differences and iteration counts, then launch times of both variants.
 

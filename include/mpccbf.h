@@ -145,7 +145,12 @@ int mpccbf_num_shared_rows(const mpccbf_ctx* ctx);
  *               re-solved in the same call by the fallback launch of the same separable solver
  *               with 8 CBF row slots per lane (128 rows; slack mode: the neighbours with a live
  *               row compacted into the 16 lanes); beyond that its QPs report ERROR (the agent's
- *               earlier iterations and every other agent are unaffected). A QP whose
+ *               earlier iterations and every other agent are unaffected). The dense layouts have
+ *               no capacity launch: with m shared box rows the 16-lane one holds 64 - m CBF rows
+ *               per agent and the 64-lane one 256 - m. The default variant takes the 16-lane one
+ *               only when no agent can exceed its slots (grid lists with knn_k x cbf_horizon <=
+ *               64 - m), else the 64-lane one; a dense layout forced by mpccbf_set_variant (1: 64
+ *               lanes x 1 slot, 3: 16 lanes x 4 slots) reports ERROR beyond 64 - m rows. A QP whose
  *               data is not finite (NaN / Inf state, target or neighbour state) reports ERROR
  *               slack_mode requires cbf_horizon <= 2 (a neighbour's lane holds its rows of two
  *               samples): with the collision controller a solve beyond it launches nothing and

@@ -87,6 +87,10 @@ struct mpccbf_ctx {
     int defer_parity = 0;
     int variant = 0;
     int last_n = 0;  // agents of the last IMPC launch (the kernel name depends on it: share-adaptive)
+    // its neighbour lists (the default variant's dense layout depends on them: caller lists, or the
+    // grid's knn_k nearest)
+    bool last_csr = false;
+    int last_knn = 0;
     // active-set store (mpccbf_set_active_store): the caller's device buffer of store_rows records,
     // or nullptr; store_min_steps as the kernels take it (>= 1, or < 0: export only)
     int32_t* store = nullptr;
@@ -306,6 +310,8 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         HIP_TRY(hipMemsetAsync(store + (size_t)b->agent_first * AS_WORDS, 0,
                                (size_t)b->num_agents * AS_WORDS * sizeof(int32_t), stream));
     c->last_n = b->num_agents;
+    c->last_csr = !grid;
+    c->last_knn = b->knn_k;
     if (fb && c->defer_cap < b->num_agents) {
         const size_t bytes = 2 * (size_t)(b->num_agents + 2) * sizeof(int32_t);
         c->defer_cap = 0;
@@ -428,13 +434,14 @@ int mpccbf_impc_solve(mpccbf_ctx* c, const mpccbf_batch* b, void* stream) {
     return impc_enqueue(c, b, (hipStream_t)stream, nullptr, nullptr, c->dev, c->store);
 }
 
-// (neither the clock waves nor the name depend on where the neighbour lists come from)
+// (the clock waves do not depend on where the neighbour lists come from: the dense layouts, whose
+// choice does, write no clock)
 int32_t mpccbf_impc_launch_waves(const mpccbf_ctx* c, int32_t num_agents) {
     return c ? ctx_plan(c, num_agents, false, 0, c->store != nullptr).clock_waves : 0;
 }
 
 const char* mpccbf_kernel_name(const mpccbf_ctx* c) {
-    return c ? ctx_plan(c, c->last_n, false, 0, c->store != nullptr).name : "";
+    return c ? ctx_plan(c, c->last_n, c->last_csr, c->last_knn, c->store != nullptr).name : "";
 }
 
 int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t min_steps) {

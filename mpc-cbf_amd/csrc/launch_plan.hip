@@ -74,6 +74,10 @@ LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int 
     const bool full16 = sep_variant && sep16;
     // some agent can exceed the 16 CBF row slots (caller lists, or k nearest x CBF samples > 16)
     const bool exceed = csr || knn_k * op.cbf_h > 16;
+    // the dense 16-lane instantiation has 64 - m CBF row slots and no capacity launch (beyond them
+    // a QP reports ERROR): the default variant takes it only when no agent can exceed them (grid
+    // lists: at most knn_k neighbours x cbf_h samples), else the 64-lane one with 256 - m slots
+    const bool dense16 = op.m < 64 && (variant == 3 || (variant == 0 && !csr && knn_k * op.cbf_h <= 64 - op.m));
 
     LaunchPlan p{};
     p.capacity = IMPC_NONE;
@@ -96,7 +100,7 @@ LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int 
             if (wide) p.kernel = p.store ? IMPC_WIDE_STORE : IMPC_WIDE;
             else if (lean) p.kernel = IMPC_SEP_LEAN;
             else if (full16) p.kernel = p.store ? IMPC_SEP_STORE : IMPC_SEP;
-            else if (op.nz == 6 && (variant == 0 || variant == 3) && op.m < 64) p.kernel = IMPC_DENSE_16_4;
+            else if (op.nz == 6 && dense16) p.kernel = IMPC_DENSE_16_4;
             else if (op.nz == 6 && variant == 1 && op.m < 64) p.kernel = IMPC_DENSE_64_1;
             else if (op.nz == 6 && op.m < 256) p.kernel = IMPC_DENSE_64_4;
             else p.kernel = IMPC_NONE;

@@ -1048,14 +1048,18 @@ struct Solver {
 
     // Equality-constrained re-solve on the active set (polish, no regularisation, two steps of
     // iterative refinement). Accepted only if its KKT certificate is no worse than the IPM's.
+    // The first attempt takes the sides the interior point holds active (z > s). Where that is
+    // refused — a weakly active side whose multiplier the interior point has not yet separated
+    // from its slack: on a slack-mode QP whose objective is ~1e6 the gap tolerance, relative to
+    // the objective, leaves the curve's weakly determined directions 1e-3 off — the set is
+    // corrected one side at a time (the most negative multiplier leaves, else the most violated
+    // side enters) and the re-solve repeated, under the same acceptance rule.
     static double merit(const double* kk, double cinf, double zinf) {
         return std::max(std::max(kk[0] / (1.0 + cinf), kk[1]), std::max(kk[2] / (1.0 + zinf), kk[3]));
     }
-    bool polish(Result& R) const {
+    bool polish_set(const std::vector<int>& act, std::vector<double>& x, std::vector<double>& lam,
+                    std::vector<double>& z) const {
         const int ns = (int)sides.size();
-        std::vector<int> act;
-        for (int k = 0; k < ns; k++)
-            if (R.z[k] > R.s[k]) act.push_back(k);
         const int na = (int)act.size();
         const int N = n + me + na;
         std::vector<double> M(N * N, 0.0), b(N, 0.0);
@@ -1095,22 +1099,80 @@ struct Solver {
             lu.solve(res);
             for (int i = 0; i < N; i++) sol[i] += res[i];
         }
-        std::vector<double> x(sol.begin(), sol.begin() + n), lam(sol.begin() + n, sol.begin() + n + me),
-            z(ns, 0.0);
+        x.assign(sol.begin(), sol.begin() + n);
+        lam.assign(sol.begin() + n, sol.begin() + n + me);
+        z.assign(ns, 0.0);
         for (int a = 0; a < na; a++) z[act[a]] = sol[n + me + a];
-        double kk[4];
-        certificate(x, lam, z, kk);
-        double cinf = 0, zi = 0, zp = 0;
-        for (double v : c) cinf = std::max(cinf, std::fabs(v));
-        for (double v : z) zp = std::max(zp, std::fabs(v));
-        for (double v : R.z) zi = std::max(zi, std::fabs(v));
-        if (!(merit(kk, cinf, zp) <= merit(R.kkt, cinf, zi))) return false;
-        R.x = x;
-        R.lam = lam;
-        R.z = z;
-        for (int k = 0; k < ns; k++) R.s[k] = sides[k].sg * (gdot(sides[k], x.data()) - sides[k].b);
-        std::memcpy(R.kkt, kk, sizeof(kk));
         return true;
+    }
+    bool polish(Result& R) const {
+        const int ns = (int)sides.size();
+        std::vector<int> act;
+        for (int k = 0; k < ns; k++)
+            if (R.z[k] > R.s[k]) act.push_back(k);
+        double cinf = 0, zi = 0;
+        for (double v : c) cinf = std::max(cinf, std::fabs(v));
+        for (double v : R.z) zi = std::max(zi, std::fabs(v));
+        const double ipm = merit(R.kkt, cinf, zi);
+        auto commit = [&](const std::vector<double>& x, const std::vector<double>& lam,
+                          const std::vector<double>& z, const double* kk) {
+            R.x = x;
+            R.lam = lam;
+            R.z = z;
+            for (int k = 0; k < ns; k++) R.s[k] = sides[k].sg * (gdot(sides[k], x.data()) - sides[k].b);
+            std::memcpy(R.kkt, kk, 4 * sizeof(double));
+        };
+        // the first attempt's solution where the acceptance rule takes it: what is kept if the
+        // corrections below do not reach a consistent set
+        bool have_first = false;
+        std::vector<double> fx, fl, fz;
+        double fk[4];
+        for (int round = 0; round < 32; round++) {
+            std::vector<double> x, lam, z;
+            if (!polish_set(act, x, lam, z)) break;
+            double kk[4], zp = 0;
+            certificate(x, lam, z, kk);
+            for (double v : z) zp = std::max(zp, std::fabs(v));
+            const bool accepted = merit(kk, cinf, zp) <= ipm;
+            if (round == 0 && accepted) {
+                have_first = true;
+                fx = x;
+                fl = lam;
+                fz = z;
+                std::memcpy(fk, kk, sizeof(kk));
+            }
+            // correct the set: an active side with a negative multiplier leaves, else the most
+            // violated inactive side enters (the merit's scales, 1 + |z|_inf ~ the slack weights,
+            // hide a multiplier of -1e-3 on a box row)
+            int drop = -1, add = -1;
+            double zmin = -1e-12 * (1.0 + zp), smin = -1e-9;
+            for (size_t a = 0; a < act.size(); a++)
+                if (z[act[a]] < zmin) {
+                    zmin = z[act[a]];
+                    drop = (int)a;
+                }
+            if (drop >= 0) {
+                act.erase(act.begin() + drop);
+                continue;
+            }
+            for (int k = 0; k < ns; k++) {
+                if (std::find(act.begin(), act.end(), k) != act.end()) continue;
+                const double sk = sides[k].sg * (gdot(sides[k], x.data()) - sides[k].b) / (1.0 + std::fabs(sides[k].b));
+                if (sk < smin) {
+                    smin = sk;
+                    add = k;
+                }
+            }
+            if (add >= 0) {
+                act.push_back(add);
+                continue;
+            }
+            if (!accepted) break;
+            commit(x, lam, z, kk);  // a consistent active set
+            return true;
+        }
+        if (have_first) commit(fx, fl, fz, fk);
+        return have_first;
     }
 };
 

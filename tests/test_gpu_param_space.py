@@ -480,13 +480,15 @@ def test_combined_case_matches_oracle(mpclib):
 
 # ---- 6. exact-reduction options -----------------------------------------------------------------
 
-def _reduction_case(mpclib, torch, k_hor, name, **opts):
+def _reduction_case(mpclib, torch, k_hor, name, variant=0, **opts):
     st, tg = C.crowded(64, 0.5, 5)
     rp, col = swarm.knn_csr(st, 8, 6.0)
     cfg = swarm.config(k_hor)
     ref = oracle_ref(("opt", k_hor), cfg, st, tg, rp, col)
     base = run_gpu(mpclib.Context(cfg), st, tg, rp, col, torch)
     ctx = mpclib.Context(cfg, **opts)
+    if variant:
+        ctx.set_variant(variant)
     g = run_gpu(ctx, st, tg, rp, col, torch)
     assert ctx.kernel_name == name, ctx.kernel_name
     np.testing.assert_array_equal(g["status"], base["status"])
@@ -500,10 +502,13 @@ def _reduction_case(mpclib, torch, k_hor, name, **opts):
 @pytest.mark.parametrize("k_hor,name", [(10, DENSE16), (15, DENSE64)])
 def test_keep_redundant_changes_no_result(mpclib, k_hor, name):
     """mpccbf_options.keep_redundant: every box row kept (57 rows at k_hor = 10, 87 at 15 — more
-    than 16 per channel, so the dense layouts run: impc_kernel<6,16,4> below 64 rows,
-    impc_kernel<6,64,4> from 64 on). Same statuses as the default context, objectives within 1e-8
-    relative, parity with the oracle."""
-    _reduction_case(mpclib, _torch(), k_hor, name, keep_redundant=True)
+    than 16 per channel, so the dense layouts run). With caller lists the default variant takes
+    impc_kernel<6,64,4> at both (at 57 rows the 16-lane instantiation has 7 CBF row slots and no
+    capacity launch). `name` is what variant 3 runs: impc_kernel<6,16,4> below 64 rows (these
+    inputs' at most 4 live rows fit its 7 slots), impc_kernel<6,64,4> from 64 on. Each: same
+    statuses as the default context, objectives within 1e-8 relative, parity with the oracle."""
+    _reduction_case(mpclib, _torch(), k_hor, DENSE64, keep_redundant=True)
+    _reduction_case(mpclib, _torch(), k_hor, name, variant=3, keep_redundant=True)
 
 
 @pytest.mark.parametrize("k_hor", [10, 15])

@@ -2,7 +2,9 @@
 
 1. Over a grid of hand-filled operators the plan gives the answers of the selection functions it
    replaced (recorded at the parent commit by tools/launch_plan_grid.cpp -DPARENT into
-   tests/golden/launch_plan_parent.txt): kernel name, clock waves, store, defer, capacity launch.
+   tests/golden/launch_plan_parent.txt): kernel name, clock waves, store, defer, capacity launch —
+   except where the default variant's dense-layout slot rule moves a
+   combination from the 16-lane to the 64-lane instantiation, which the test computes itself.
 2. For real configurations (mpccbf_host_launch_plan) the names are the literals the GPU tests
    assert after their solves, and the packed buffer keeps its invariants."""
 import os
@@ -44,9 +46,43 @@ def test_plan_equals_the_parents_selection_functions():
     # 6 bases x 31 single-field variations; 6 variants x 4 counts x store x csr x knn_k, + 4 with connectivity
     assert len(want) == 186 and all(len(v) == 196 for v in want.values())
     assert list(got) == list(want)
+    # One rule has changed since the fixture was recorded: the default variant takes the dense
+    # 16-lane instantiation (64 - m CBF row slots, no capacity launch) only when no agent can exceed
+    # its slots — grid lists with knn_k x cbf_h <= 64 - m — and the 64-lane one otherwise. The
+    # combinations that move are computed here from that rule and the grid's own operators
+    # (tools/launch_plan_grid.cpp: m and cbf_h of the base, one field varied per point); for them
+    # the parent's token holds with the kernel name alone replaced; every other one is the parent's.
+    base_m = {"sep15": 48, "slack16": 48, "slack32": 51, "dense6": 48, "fov": 60, "fovslack": 60}
+    combos = [(variant, n, store, csr, knn) for variant in range(6) for n in (0, 5, 1024, 1025)
+              for store in (0, 1) for csr in (0, 1) for knn in (8, 9)]
+    moved = {}
     for label, toks in want.items():
-        diff = [(i, t, g) for i, (t, g) in enumerate(zip(toks, got[label])) if t != g]
-        assert not diff and len(got[label]) == len(toks), (label, diff[:3])
+        base, field = label.split("/")
+        name, value = field.split("=")
+        m = int(value) if name == "m" else base_m[base]
+        cbf_h = int(value) if name == "cbf_h" else 2
+        assert len(got[label]) == len(toks) == len(combos) + 4
+        for i, (t, g) in enumerate(zip(toks, got[label])):
+            expect = t
+            if i < len(combos):  # (the last four: connectivity attached)
+                variant, _, _, csr, knn = combos[i]
+                if variant == 0 and t.startswith(DENSE16 + "|") and (csr or knn * cbf_h > 64 - m):
+                    assert m < 64
+                    expect = DENSE64 + t[len(DENSE16):]
+                    moved.setdefault(label, []).append(i)
+            assert g == expect, (label, i, t, g)
+    # the moved set: caller lists at every dense point; grid lists where knn_k x cbf_h exceeds the
+    # slots (9 x 2 > 16 at m = 48, 8 x 3 > 16, 8 x 2 > 1 at m = 63) and not where it does not
+    assert moved and all(b in ("sep15", "dense6") for b in {k.split("/")[0] for k in moved})
+    grid16 = [i for i, c in enumerate(combos) if c[0] == 0 and not c[3] and c[4] == 8]
+    assert not set(grid16) & set(moved["dense6/lean=0"]) and set(grid16) <= set(moved["dense6/m=63"])
+    assert set(grid16) <= set(moved["dense6/cbf_h=3"])
+    assert len(moved["dense6/lean=0"]) == 4 * 2 * 3  # counts x store x (csr 8, csr 9, grid 9)
+    # the separable kernels' answers (the benchmarked paths) are all the parent's
+    for label, toks in want.items():
+        for i, t in enumerate(toks):
+            if "sep" in t.split("|")[0] or "wide" in t.split("|")[0]:
+                assert got[label][i] == t
 
 
 # configuration -> variant -> the name the GPU tests assert for 64 agents (test_gpu_param_space.py

@@ -49,9 +49,13 @@ static hipError_t launch_impc_dense(int blocks, int block_size, const DevOps& op
 //       the 16-lane kernel (4 agents per wave: one wave per SIMD covers 4 x as many agents);
 //   4 — the 16-lane kernel at any count (the layout of rounds 1-4);
 //   5 — the one-agent-per-wave kernel at any count.
-// (Round 6, measured and dropped: a lean-then-full variant — the fast start and the dual active
-// set, the full pipeline in place after the IMPC loop for the agents they do not settle — ran the
-// lean part 1.6 us slower than the lean kernel alone and 0.5 us slower than the full kernel.)
+// The 16-lane main launch (IMPC_SEP) runs the lean pipeline — the fast start and the dual active set
+// — inline and finishes the agents they do not settle with an out-of-line call of the full pipeline
+// in the same wave (impc_sep_complete, impc_sep.hpp): 1.2 us per config-3 step under the kernel that
+// had the interior-point solver inlined. (Round 6, measured and dropped: the same split with the
+// full pipeline inlined after the IMPC loop ran the lean part 1.6 us slower than the lean kernel
+// alone and 0.5 us slower than the full kernel.) IMPC_SEP_LEAN is the two-launch form of the split
+// (mpccbf_options.lean): the unsettled agents go to the queue and IMPC_QUEUE1.
 // Capacity launches (IMPC_QUEUE*): the agents the main launch deferred (the queue in a.queue):
 //   slack mode, more than 16 neighbours — the slack solver, the neighbours with a live row
 //   compacted into the lanes;

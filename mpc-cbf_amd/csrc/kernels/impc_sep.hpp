@@ -319,14 +319,21 @@ __device__ __forceinline__ SepRows<SB, CB>& pick_rows(SepRows<SB, CB>& reg, SepR
 // CONN (connectivity attached, mpccbf_set_connectivity; impc_conn.hip alone instantiates it): the
 // team's connectivity rows are staged behind the safety rows of every iteration (conn_rows.hpp);
 // rows in LDS as the capacity launch keeps them.
-template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false, bool STORE = false, bool CONN = false>
+// HANDOVER (with LEAN: the main launch that completes in-kernel, impc_sep_complete): a QP the lean
+// pipeline does not settle makes the agent set *handed and return instead of deferring it — nothing
+// but per-iteration outputs, the neighbour list and stamps has been written by then, all of which the
+// full pipeline's run from scratch rewrites with the same values. (A flag, not a return value: the
+// other instantiations' code stays what it was, tools/code_sizes.py.)
+template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false, bool STORE = false, bool CONN = false,
+          bool HANDOVER = false>
 __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args,
                                const int ai, const int gl, double* stage, double* red, NbScratch& nbs,
                                double* keep, SepRowsLds<SB, CB>* rows_lds = nullptr, double* bconst = nullptr,
                                int32_t* astore = nullptr, const StoreArgs store = StoreArgs{nullptr, 0},
-                               const ConnArgs conn = ConnArgs{}) {
+                               const ConnArgs conn = ConnArgs{}, bool* handed = nullptr) {
     static_assert(!(STORE && SLACK), "the active-set store is not built for slack mode");
     static_assert(!CONN || (!SLACK && !STORE && !LEAN), "connectivity rows: the full non-slack pipeline");
+    static_assert(!HANDOVER || (LEAN && !STORE), "only the lean pipeline hands an agent over");
     constexpr int G = 16;
     constexpr int NZ = SEP_NZ;
     constexpr int cap = CB * G;  // CBF rows per agent
@@ -585,7 +592,8 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
         } else if constexpr (LEAN) {
             // lean main launch: the fast start and the dual active set only. A QP that needs more
             // (the active set gives up, or no feasible point without a certificate well above the
-            // tolerance: phase 1) defers the whole agent to the fallback launch, which runs the
+            // tolerance: phase 1) defers the whole agent to the fallback launch (HANDOVER: returns
+            // it to the wrapper for the in-kernel completion), which runs the
             // full pipeline (PDIP attempts, phase 1) on the same inputs — so the main kernel's
             // registers are those of the active-set path, not the interior-point solver's.
             const double* Pi = opp(buf, op.o_Pinv);
@@ -599,7 +607,8 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             double tl = 0.0, prs = __builtin_nan(""), drs = __builtin_nan("");
             const int k0 = warm_count(it);
             const int r = sep_dual_as<G, SB, CB>(rw, live, opp(buf, op.o_Pr), Pi, q, yu, op.tol, op.dual_as, stage, y,
-                                                 prs, drs, nit, nullptr, true, tl, nullptr, k0, act,
+                                                 prs, drs, nit, nullptr, HANDOVER ? args.dual_res != nullptr : true, tl,
+                                                 nullptr, k0, act,
                                                  (STORE || it == 0) ? act : nullptr, nullptr, bsc, bw);
             if (r > 0) {
                 st = ST_OPTIMAL;
@@ -607,6 +616,9 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
                 st = ST_INFEASIBLE;
                 prs = tl;
                 drs = __builtin_nan("");
+            } else if constexpr (HANDOVER) {
+                *handed = true;
+                return;
             } else {
                 defer_agent(args, agent(), gl);
                 return;
@@ -785,9 +797,49 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     stamp(args, ai, gl, 7);
 }
 
+// The kernel-argument segment of impc_sep_kernel as a struct: each argument at its natural alignment
+// in declaration order (the hidden arguments follow the last one).
+struct SepKernargs {
+    DevOps op;
+    const double* buf;
+    ImpcArgs args;
+};
+static_assert(offsetof(SepKernargs, buf) == ((sizeof(DevOps) + 7) & ~size_t(7)) &&
+                  offsetof(SepKernargs, args) == offsetof(SepKernargs, buf) + 8 && alignof(ImpcArgs) <= 8 &&
+                  alignof(DevOps) <= 8,
+              "SepKernargs mirrors the kernel-argument layout");
+
+template <class T>
+using lds_ptr = __attribute__((address_space(3))) T*;
+
+// In-kernel completion of the 16-lane main launch: the full pipeline (PDIP attempts, phase 1) from
+// scratch for an agent the lean pipeline handed over (impc_sep_agent's HANDOVER), on the group's own
+// LDS slices. Out of line, so that the main kernel's hot path is the lean pipeline's code and
+// registers; it takes nothing from the caller but the agent index, the slices as LDS-typed pointers
+// and the address of the kernel-argument segment (ka_lo, ka_hi: as a value, made wave-uniform again
+// here — the segment-pointer intrinsic itself is null outside a kernel): the operators and the launch
+// arguments are re-read from the segment with scalar loads (as arguments by reference they were copied
+// to the stack at every launch's start). Internal linkage and never a tail call: the caller then
+// knows which registers the callee leaves alone and the callee saves none (inter-procedural register
+// allocation), which keeps its frame at its own spills (40 B/lane; 1,368 with the saves).
+template <int SB, int CB>
+static __device__ __attribute__((noinline, not_tail_called)) void impc_sep_complete(
+    const int ai, const unsigned ka_lo, const unsigned ka_hi, lds_ptr<double> stage, lds_ptr<double> red,
+    lds_ptr<NbScratch> nbs, lds_ptr<double> keep, lds_ptr<double> bconst) {
+    const unsigned long long kp = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)ka_hi) << 32) |
+                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)ka_lo);
+    const SepKernargs* ka = (const SepKernargs*)(const __attribute__((address_space(4))) SepKernargs*)kp;
+    impc_sep_agent<SB, CB, false, false>(ka->op, ka->buf, ka->args, ai, (int)(threadIdx.x & 15u), (double*)stage,
+                                         (double*)red, *(NbScratch*)nbs, (double*)keep, nullptr, (double*)bconst);
+}
+
 // QUEUE = false: one agent per 16-lane group. QUEUE = true (fallback launch): the agents the main
 // launch deferred (args.queue: [count, blocks done, agents...]), one per group (the grid covers
 // every agent of the batch); the last block to finish empties the queue for the next step.
+// The plain main launch (no slack, not LEAN) runs the lean pipeline — fast start and dual active set
+// — inline and finishes the agents it does not settle with a call of impc_sep_complete once the
+// wave's four groups have come back: one launch, the hot path without the interior-point solver's
+// code. LEAN is the two-launch form of the same split (the unsettled agents go to the queue).
 template <int SB, int CB, bool SLACK, int BS, bool QUEUE = false, bool LEAN = false>
 __global__ void __launch_bounds__(BS) impc_sep_kernel(const DevOps op, const double* __restrict__ buf,
                                                        const ImpcArgs args) {
@@ -813,10 +865,27 @@ __global__ void __launch_bounds__(BS) impc_sep_kernel(const DevOps op, const dou
         grid_clear<BS>(args);
         const int ai = xcd_block((int)blockIdx.x, (int)gridDim.x) * GPB + gib;
         if (ai >= args.num_agents) return;
-        impc_sep_agent<SB, CB, SLACK, false, LEAN>(op, buf, args, ai, gl, stage_all[gib], red_all[gib],
-                                                   nb_scratch[gib], keep_all[gib],
-                                                   rows_lds + (rows_lds_per_lane ? gib * 16 : 0),
-                                                   SLACK ? nullptr : bconst_all[SLACK ? 0 : gib]);
+        if constexpr (!SLACK && !LEAN) {
+            static_assert(!rows_lds_per_lane, "the completion keeps its rows in registers");
+            // (the lean agent uses a prefix of the full pipeline's keep area; without the dual active
+            // set — the PDIP-only diagnostic setting — every agent takes the completion)
+            bool left = op.dual_as <= 0;
+            if (!left)
+                impc_sep_agent<SB, CB, false, false, true, false, false, true>(
+                    op, buf, args, ai, gl, stage_all[gib], red_all[gib], nb_scratch[gib], keep_all[gib], nullptr,
+                    bconst_all[gib], nullptr, StoreArgs{nullptr, 0}, ConnArgs{}, &left);
+            const unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+            if (left)
+                impc_sep_complete<SB, CB>(ai, (unsigned)kp, (unsigned)(kp >> 32), (lds_ptr<double>)stage_all[gib],
+                                          (lds_ptr<double>)red_all[gib],
+                                          (lds_ptr<NbScratch>)&nb_scratch[gib], (lds_ptr<double>)keep_all[gib],
+                                          (lds_ptr<double>)bconst_all[gib]);
+        } else {
+            impc_sep_agent<SB, CB, SLACK, false, LEAN>(op, buf, args, ai, gl, stage_all[gib], red_all[gib],
+                                                       nb_scratch[gib], keep_all[gib],
+                                                       rows_lds + (rows_lds_per_lane ? gib * 16 : 0),
+                                                       SLACK ? nullptr : bconst_all[SLACK ? 0 : gib]);
+        }
         kclock_end<BS>(args);
     } else {
         // one queue entry per group (no grid-stride loop: carried across iterations the agent's

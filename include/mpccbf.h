@@ -139,7 +139,14 @@ int mpccbf_num_shared_rows(const mpccbf_ctx* ctx);
  *               launch sequence (spatial hash of `states` + in-kernel 3x3-cell query; in
  *               mpccbf_run_steps the IMPC kernel itself fills the next step's hash table);
  *               knn_k <= 16; any number of agents within the radius (beyond 64 candidates the
- *               query streams them through a running k-nearest set)
+ *               query streams them through a running k-nearest set).
+ *               The contract of every query (and of mpccbf_build_neighbors): j != self; squared
+ *               distance dx*dx + dy*dy <= knn_radius^2 as computed in double (inclusive); the
+ *               knn_k nearest, ties broken by the smaller agent index; the list sorted by index.
+ *               The hash cells have edge knn_radius * (1 + 2^-20), so that the rounding of the
+ *               cell coordinates never hides a neighbour within the radius from the 3x3-cell
+ *               query: guaranteed for |x|, |y| <= 2^30 * knn_radius (derivation at grid_inv_cell,
+ *               kernels/impc.hpp).
  *               Capacity: the default separable kernel keeps up to 16 live (unfiltered) CBF rows
  *               per IMPC iteration and agent (slack mode: 16 neighbours); an agent beyond it is
  *               re-solved in the same call by the fallback launch of the same separable solver

@@ -265,7 +265,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         a.grid.slots = slots[rd];
         a.grid.sst = sst[rd];
         a.grid.mask = T - 1;
-        a.grid.inv_cell = 1.0 / b->knn_radius;
+        a.grid.inv_cell = grid_inv_cell(b->knn_radius);  // (as launch_grid_insert's)
         a.grid.radius = b->knn_radius;
         a.grid.k = b->knn_k;
         // FoV controller: only agents inside the field of view are observed neighbours

@@ -81,7 +81,8 @@ constexpr int WBOX_ROW = 16 + 6 + 2;
 constexpr int SEP_ROW = 10;
 constexpr int SEP_NZD_HOST = 2;  // reduced variables per channel the separable kernel handles
 
-// Spatial hash of agent positions (uniform cells of edge `radius`) with fixed-capacity buckets:
+// Spatial hash of agent positions (uniform cells of edge `radius` plus a rounding margin,
+// grid_inv_cell) with fixed-capacity buckets:
 // bucket h holds the state rows slots[h * GRID_CAP + j], j < cnt[h], in insertion order
 // (bucket-major, round 6: a query touches one line of a cell's entries and two of its slot states;
 // slot-major, the one-agent-per-wave query's unconditional loads of the 3 x 3 cells' 7 inline
@@ -134,6 +135,18 @@ __device__ inline void grid_insert(const GridArgs& g, double x, double y, double
         *d = make_double4(x, y, vx, vy);
     }
 }
+
+// 1 / cell edge for a query of radius r: the one value every insert and every query of a table
+// takes (GridArgs::inv_cell, the CSR builder's inv). The edge is r (1 + 2^-20), a hair more than
+// the radius: with an edge of exactly r, two agents whose computed squared distance is <= r^2 can
+// land two cells apart — the subtraction nx - px, the reciprocal and the products x * inv are all
+// rounded (r = 5: x = 10 - 2 ulp and x + 5 give floor 1 and 3) — and a 3 x 3 query then never sees
+// the neighbour. Bound (u = 2^-53): computed d2 <= r^2 gives |bx - ax| <= r (1 + 4u); inv carries
+// 2u of relative error and each product u more, so the cell coordinates t = fl(x * inv) satisfy
+// t_b - t_a <= (1 + 4u) / (1 + 2^-20) + 6u X, X = max |x| / r, which is <= 1 (cells at most one
+// apart) for X <= 2^30: 6u 2^30 = 0.75 * 2^-20. Neighbour sets do not depend on the cell edge
+// otherwise (candidates are filtered by distance and ordered by (distance, index)).
+inline double grid_inv_cell(double radius) { return 1.0 / (radius * (1.0 + 0x1p-20)); }
 
 // hash table size for n agents: power of two >= n (>= 1024)
 inline uint32_t grid_table_size(int n) {

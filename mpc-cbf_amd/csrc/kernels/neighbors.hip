@@ -2,8 +2,8 @@
 //
 // The reference hands every other robot to the controller (ConnectivityIMPCCBF.cpp:59-67);
 // `all` mode reproduces that. `knn` mode keeps the k nearest (planar) within a radius using a
-// spatial hash of uniform cells (cell edge = radius): count -> scan -> scatter -> 3x3-cell
-// query. Output rows are sorted by neighbour index so results do not depend on hash order.
+// spatial hash of uniform cells (cell edge = radius plus a rounding margin, grid_inv_cell):
+// count -> scan -> scatter -> 3x3-cell query. Output rows are sorted by neighbour index so results do not depend on hash order.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -223,7 +223,7 @@ int launch_neighbors(const double* states, int num_states, int first, int num_ag
     p += align256((size_t)num_states * 4);
     int32_t* wide = (int32_t*)p;
     (void)scratch_bytes;
-    const double inv = 1.0 / radius;
+    const double inv = grid_inv_cell(radius);
     hipError_t e = hipMemsetAsync(cnt, 0, (size_t)T * 4, s);
     if (e != hipSuccess) return (int)e;
     const int nb = (num_states + 255) / 256;
@@ -286,7 +286,7 @@ hipError_t launch_grid_insert(const double* states, int n, int skip0, int skip1,
     g.ins_slots = slots;
     g.ins_sst = sst;
     g.mask = grid_table_size(n) - 1u;
-    g.inv_cell = 1.0 / radius;
+    g.inv_cell = grid_inv_cell(radius);
     hipLaunchKernelGGL(dev::grid_insert_kernel, dim3((m + 255) / 256), dim3(256), 0, s, states, n, skip0, skip1, g);
     return hipGetLastError();
 }

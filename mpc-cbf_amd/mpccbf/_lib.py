@@ -476,7 +476,7 @@ class Context:
                   status=None, obj=None, iters=None, status_log=None, iters_log=None,
                   timing=False, comm=None, reserve_steps=0, solve_stride=1, step_timing=True,
                   stream=None, traj_t=None, pos_std=0.0, vel_std=0.0, noise_seed=0, step_index=0,
-                  cov=None, kernel_clock=None, stamps=None, continue_tables=False):
+                  cov=None, kernel_clock=None, stamps=None, continue_tables=False, nb_out=None):
         """The arguments of one mpccbf_run_steps call, marshalled once (checks, ctypes structures,
         the stream handle): returns a PreparedRun whose call () runs the steps — a caller that
         times the steps prepares them outside its timed region. The call returns a dict with the
@@ -485,7 +485,8 @@ class Context:
         (num_steps, W, 2) device tensor (torch.int64, W >= launch_waves(num_agents)) for every
         wave's start / end of every IMPC launch (s_memrealtime, 100 MHz ticks; zero: no wave);
         kernel_clock_us() turns it into per-launch durations. stamps: the diagnostics builds' phase
-        stamps (as impc_solve; every step overwrites them)."""
+        stamps (as impc_solve; every step overwrites them). nb_out: as impc_solve (every step
+        overwrites it: it ends holding the lists of the last step)."""
         if num_agents is None:
             num_agents = states.shape[0] - agent_first
         self._last_knn = (int(knn_k), float(knn_radius))
@@ -502,7 +503,8 @@ class Context:
                   status=_ptr(status), obj=_ptr(obj), iters=_ptr(iters), next_states=None,
                   knn_k=int(knn_k), knn_radius=float(knn_radius), stamps=_ptr(stamps),
                   traj_t=_ptr(traj_t), pos_std=float(pos_std), vel_std=float(vel_std),
-                  noise_seed=int(noise_seed), step_index=int(step_index), cov=_ptr(cov))
+                  noise_seed=int(noise_seed), step_index=int(step_index), cov=_ptr(cov),
+                  nb_out=_ptr(nb_out))
         step_ms = np.zeros(max(num_steps, 1), dtype=np.float32) if timing and step_timing else None
         solve_ms = np.zeros(max(num_steps, 1), dtype=np.float32) if timing else None
         r = Run(num_steps=num_steps, states_alt=_ptr(states_alt), status_log=_ptr(status_log),
@@ -515,7 +517,7 @@ class Context:
                 continue_tables=int(bool(continue_tables)))
         return PreparedRun(self, b, r, _stream(stream), states, states_alt, num_steps, step_ms, solve_ms,
                            keep=(targets, refs, nb_row_ptr, nb_col, x, status, obj, iters, status_log,
-                                 iters_log, traj_t, cov, kernel_clock, stamps))
+                                 iters_log, traj_t, cov, kernel_clock, stamps, nb_out))
 
     def launch_waves(self, num_agents: int) -> int:
         """Waves of the IMPC launch for num_agents that write the launch clock (0: no clock)."""

@@ -347,22 +347,37 @@ __device__ int grid_neighbors_finish(const ImpcArgs& args, int self, double px, 
             // two candidates per lane (slots gl, gl + 16) compared against all by DPP row
             // broadcasts, in registers; then ordered by agent index the same way
             const bool v0 = gl < cnt, v1 = gl + G < cnt;
-            const double d0 = v0 ? sc.d2[gl] : 1e300, d1 = v1 ? sc.d2[gl + G] : 1e300;
             const int j0 = v0 ? sc.idx[gl] : 0x7fffffff, j1 = v1 ? sc.idx[gl + G] : 0x7fffffff;
-            int r0 = 0, r1 = 0;
-            auto rank_step = [&](double dm, int jm) {
-                r0 += nb_before(dm, jm, d0, j0) ? 1 : 0;
-                r1 += nb_before(dm, jm, d1, j1) ? 1 : 0;
-            };
+            // two short cuts, both with the full path's outcome. No more than k candidates: each
+            // one's rank is at most cnt - 1 < k, so all are kept unranked. No more than G: slot 1
+            // is empty in every lane, and only slot 0's broadcasts are made. The conditions are
+            // group-uniform (a DPP row is one group) and tested over the wave, so the branches are
+            // scalar; a group that needs neither then takes the longer path to the same result.
+            const bool ranked = __ballot(cnt > k) != 0ull;
+            const bool two = __ballot(cnt > G) != 0ull;
+#define MPCCBF_NB_16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
+            bool k0 = v0, k1 = v1;
+            if (ranked) {
+                const double d0 = v0 ? sc.d2[gl] : 1e300, d1 = v1 ? sc.d2[gl + G] : 1e300;
+                int r0 = 0, r1 = 0;
+                auto rank_step = [&](double dm, int jm) {
+                    r0 += nb_before(dm, jm, d0, j0) ? 1 : 0;
+                    r1 += nb_before(dm, jm, d1, j1) ? 1 : 0;
+                };
+#define MPCCBF_NB_RANK0(K) r0 += nb_before(row_bcast_k<K>(d0), row_bcast_i<K>(j0), d0, j0) ? 1 : 0;
 #define MPCCBF_NB_RANK(K)                                           \
     rank_step(row_bcast_k<K>(d0), row_bcast_i<K>(j0));              \
     rank_step(row_bcast_k<K>(d1), row_bcast_i<K>(j1));
-            MPCCBF_NB_RANK(0) MPCCBF_NB_RANK(1) MPCCBF_NB_RANK(2) MPCCBF_NB_RANK(3)
-            MPCCBF_NB_RANK(4) MPCCBF_NB_RANK(5) MPCCBF_NB_RANK(6) MPCCBF_NB_RANK(7)
-            MPCCBF_NB_RANK(8) MPCCBF_NB_RANK(9) MPCCBF_NB_RANK(10) MPCCBF_NB_RANK(11)
-            MPCCBF_NB_RANK(12) MPCCBF_NB_RANK(13) MPCCBF_NB_RANK(14) MPCCBF_NB_RANK(15)
+                if (two) {
+                    MPCCBF_NB_16(MPCCBF_NB_RANK)
+                } else {
+                    MPCCBF_NB_16(MPCCBF_NB_RANK0)
+                }
 #undef MPCCBF_NB_RANK
-            const bool k0 = v0 && r0 < k, k1 = v1 && r1 < k;
+#undef MPCCBF_NB_RANK0
+                k0 = v0 && r0 < k;
+                k1 = v1 && r1 < k;
+            }
             // order the kept set by agent index: position = kept candidates with a smaller index
             const int jk0 = k0 ? j0 : 0x7fffffff, jk1 = k1 ? j1 : 0x7fffffff;
             int p0 = 0, p1 = 0;
@@ -370,12 +385,16 @@ __device__ int grid_neighbors_finish(const ImpcArgs& args, int self, double px, 
                 p0 += jm < j0 ? 1 : 0;
                 p1 += jm < j1 ? 1 : 0;
             };
+#define MPCCBF_NB_POS0(K) p0 += row_bcast_i<K>(jk0) < j0 ? 1 : 0;
 #define MPCCBF_NB_POS(K) pos_step(row_bcast_i<K>(jk0)); pos_step(row_bcast_i<K>(jk1));
-            MPCCBF_NB_POS(0) MPCCBF_NB_POS(1) MPCCBF_NB_POS(2) MPCCBF_NB_POS(3)
-            MPCCBF_NB_POS(4) MPCCBF_NB_POS(5) MPCCBF_NB_POS(6) MPCCBF_NB_POS(7)
-            MPCCBF_NB_POS(8) MPCCBF_NB_POS(9) MPCCBF_NB_POS(10) MPCCBF_NB_POS(11)
-            MPCCBF_NB_POS(12) MPCCBF_NB_POS(13) MPCCBF_NB_POS(14) MPCCBF_NB_POS(15)
+            if (two) {
+                MPCCBF_NB_16(MPCCBF_NB_POS)
+            } else {
+                MPCCBF_NB_16(MPCCBF_NB_POS0)
+            }
 #undef MPCCBF_NB_POS
+#undef MPCCBF_NB_POS0
+#undef MPCCBF_NB_16
             wave_lds_sync();  // every lane has read its candidates
             if (k0) {
                 sc.idx[p0] = j0;

@@ -538,6 +538,87 @@ typedef struct mpccbf_fov_control_batch {
 int mpccbf_fov_control_solve(const mpccbf_fov_control_params* p, const mpccbf_fov_control_batch* b,
                              int32_t device, void* hip_stream);
 
+/* ---- Batched particle filters for the FoV controllers' neighbour estimates (feature macro;
+ * MPCCBF_ABI_VERSION is unchanged: no struct changed layout) ---------------------------------
+ *
+ * One particle filter per (observer, neighbour) pair, over the neighbour's planar position:
+ * pf::ParticleFilter (particle_filter/src/detail/particle_filter.cpp) driven by
+ * PFApplications::processFovUpdate (particle_filter/src/pf_applications.cpp:6-44), as
+ * cbf/examples/fov/CBFControl_example.cpp:96-99,145-168,192-194 sets it up. No context needed; all
+ * pointers are device pointers; asynchronous on the stream.
+ *
+ * Pairs are the entries of a CSR list: observer agent_first + i (a row of `states`) holds the pairs
+ * e = nb_row_ptr[i] .. nb_row_ptr[i+1]-1, pair e estimates row nb_col[e] of `states`, and e indexes
+ * every per-pair buffer (nb_row_ptr[0] may be nonzero: a call works on the pairs nb_row_ptr[0] ..
+ * nb_row_ptr[0] + num_pairs - 1 and leaves every other pair's rows untouched, so observers can be
+ * split over calls or ranks on shared buffers). A pair whose nb_col entry is not a row of `states`
+ * is skipped.
+ *
+ * mpccbf_pf_init (ParticleFilter::init, particle_filter.cpp:12-56): particles = x0 + chol(init_cov) z,
+ * weights 1 / P, est_xy = x0, est_cov = init_cov, flags 0; x0 = the neighbour's position in `states`
+ * or, when init_xy is given, init_xy[e].
+ *
+ * mpccbf_pf_step (processFovUpdate), per pair:
+ *   1. predict: p += input[e] dt + W z, z ~ N(0, I) per particle; W = `process` is a plain matrix
+ *      multiplier, as in the reference (particle_filter.cpp:63-75); input NULL = 0
+ *   2. negative information: w /= weight_reduction for every particle inside the observer's field of
+ *      view (math::insideFOV, Geometry.cpp:59-73: |bearing| <= fov / 2 and distance <= Rs)
+ *   3. only if the neighbour's position in `states` is inside the observer's field of view:
+ *      w = exp(-1/2 d^T R^-1 d), d = particle - that position, R = meas_cov; normalised to sum 1
+ *      (this overwrites the weights of 2, as in the reference)
+ *   4. multinomial resampling: P draws u in [0, 1), ancestor = the first j with
+ *      u < (sum_{i<=j} w_i) / sum w, clamped to P - 1 (std::discrete_distribution's rule); the new
+ *      particle and weight are the ancestor's; the weights are not renormalised
+ *   5. est_xy = mean of the particles, est_cov = sum (p - mean)(p - mean)^T / (P - 1) as
+ *      (cxx, cxy, cyy): the row formats of mpccbf_fov_control_batch.nb_xy / nb_cov
+ * Where the reference is undefined (a zero weight sum): when the sum of the weights is 0 or not
+ * finite after 2 or after 3, the weights become 1 / P and bit 1 of the pair's flag word is set.
+ * Bit 0 of the flag word: the neighbour was measured this step (3 ran).
+ *
+ * Randomness is counter-based: every draw is a pure function of (seed, step_index, the observer's
+ * row in `states`, the neighbour's row, particle, component) — components 0 / 1 the x / y normal of
+ * the predict, 2 the resampling uniform, 3 / 4 the x / y normal of init — so a call repeats bit for
+ * bit and a pair's results do not depend on the split of the observers over calls.
+ *
+ * Refused with MPCCBF_ERR_INVALID_ARGUMENT on the host, before any device call: num_particles
+ * outside 2 .. 1024, init_cov or meas_cov not positive definite, weight_reduction <= 0, a negative
+ * count, agent_first + num_agents > num_states, a NULL required pointer (states, nb_row_ptr, nb_col,
+ * particles, weights, est_xy, est_cov) with num_pairs > 0. num_pairs == 0 or num_agents == 0:
+ * MPCCBF_OK, nothing launched. */
+#define MPCCBF_HAS_PF 1
+typedef struct mpccbf_pf_params {
+    int32_t num_particles;    /* P, 2 .. 1024 */
+    double init_cov[3];       /* (cxx, cxy, cyy) of the initial particle cloud */
+    double process[4];        /* W, row-major 2 x 2 */
+    double meas_cov[3];       /* R as (cxx, cxy, cyy) */
+    double dt;                /* the reference hard-codes 0.2 (particle_filter.cpp:19) */
+    double fov, Rs;           /* the observers' field of view (rad) and sensing range */
+    double weight_reduction;  /* pf_applications.h's weight_reduction_factor */
+    uint64_t seed;
+} mpccbf_pf_params;
+
+typedef struct mpccbf_pf_batch {
+    int32_t num_states;
+    const double* states;      /* num_states x 6 */
+    int32_t agent_first;
+    int32_t num_agents;        /* row i of nb_row_ptr is observer agent_first + i */
+    const int32_t* nb_row_ptr; /* num_agents + 1 */
+    const int32_t* nb_col;
+    int32_t num_pairs;         /* nb_row_ptr[num_agents] - nb_row_ptr[0] (the host knows it) */
+    const double* input;       /* pairs x 2 (ux, uy), or NULL */
+    const double* init_xy;     /* pairs x 2, or NULL; mpccbf_pf_init only */
+    double* particles;         /* pairs x 2 x P: x then y */
+    double* weights;           /* pairs x P */
+    double* est_xy;            /* out, pairs x 2 */
+    double* est_cov;           /* out, pairs x 3 */
+    int32_t* flags;            /* out, pairs, or NULL */
+    int32_t* ancestors;        /* out, pairs x P, or NULL: the resampling's choices (mpccbf_pf_step) */
+    int64_t step_index;
+} mpccbf_pf_batch;
+
+int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* hip_stream);
+int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* hip_stream);
+
 /* ---- Batched CBF-only connectivity controller (ConnectivityControl::optimize,
  * cbf/src/controller/ConnectivityControl.cpp:22-99) for teams of robots ----------------------
  * Per robot of a team (<= 16 robots; robots of team t are rows team_ptr[t] .. team_ptr[t+1]-1):

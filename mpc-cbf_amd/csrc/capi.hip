@@ -24,6 +24,7 @@
 #include "kernels/cbf_control.hpp"
 #include "kernels/conn_rows.hpp"
 #include "kernels/launch_plan.hpp"
+#include "kernels/pf_fov.hpp"
 
 namespace mpccbf {
 
@@ -1008,6 +1009,78 @@ int mpccbf_fov_control_solve(const mpccbf_fov_control_params* p, const mpccbf_fo
     a.nb_cov = b->nb_cov;
     HIP_TRY(launch_fov_control(a, (hipStream_t)stream));
     return MPCCBF_OK;
+}
+
+// mpccbf_pf_init / mpccbf_pf_step: every argument check runs on the host before any device call
+static int pf_call(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream,
+                   bool init) {
+    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    if (p->num_particles < PF_MIN_PARTICLES || p->num_particles > PF_MAX_PARTICLES)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_particles must be in 2 .. 1024");
+    auto pos_def = [](const double* c) {
+        return c[0] > 0.0 && c[0] * c[2] - c[1] * c[1] > 0.0 && std::isfinite(c[0]) && std::isfinite(c[1]) &&
+               std::isfinite(c[2]);
+    };
+    if (!pos_def(p->init_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "init_cov must be positive definite");
+    if (!pos_def(p->meas_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "meas_cov must be positive definite");
+    if (!(p->weight_reduction > 0.0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "weight_reduction must be positive");
+    if (b->num_states < 0 || b->num_agents < 0 || b->num_pairs < 0 || b->agent_first < 0)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "negative count");
+    if ((int64_t)b->agent_first + b->num_agents > b->num_states)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent_first + num_agents exceeds num_states");
+    if (b->num_pairs == 0 || b->num_agents == 0) return MPCCBF_OK;
+    if (!b->states || !b->nb_row_ptr || !b->nb_col || !b->particles || !b->weights || !b->est_xy || !b->est_cov)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT,
+                    "states, nb_row_ptr, nb_col, particles, weights, est_xy and est_cov are required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    PfArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.num_particles = p->num_particles;
+    a.num_states = b->num_states;
+    a.states = b->states;
+    a.agent_first = b->agent_first;
+    a.num_agents = b->num_agents;
+    a.nb_row_ptr = b->nb_row_ptr;
+    a.nb_col = b->nb_col;
+    a.num_pairs = b->num_pairs;
+    a.input = b->input;
+    a.init_xy = b->init_xy;
+    a.particles = b->particles;
+    a.weights = b->weights;
+    a.est_xy = b->est_xy;
+    a.est_cov = b->est_cov;
+    a.flags = b->flags;
+    a.ancestors = b->ancestors;
+    a.step_index = b->step_index;
+    a.seed = p->seed;
+    for (int i = 0; i < 3; i++) a.init_cov[i] = p->init_cov[i];
+    // Eigen::LLT of init_cov (particle_filter.cpp:38-39)
+    a.init_chol[0] = std::sqrt(p->init_cov[0]);
+    a.init_chol[1] = p->init_cov[1] / a.init_chol[0];
+    a.init_chol[2] = std::sqrt(p->init_cov[2] - a.init_chol[1] * a.init_chol[1]);
+    for (int i = 0; i < 4; i++) a.process[i] = p->process[i];
+    // cov.inverse() of the measurement covariance (particle_filter.cpp:96)
+    const double det = p->meas_cov[0] * p->meas_cov[2] - p->meas_cov[1] * p->meas_cov[1];
+    a.meas_inv[0] = p->meas_cov[2] / det;
+    a.meas_inv[1] = -p->meas_cov[1] / det;
+    a.meas_inv[2] = p->meas_cov[0] / det;
+    a.dt = p->dt;
+    a.fov = p->fov;
+    a.Rs = p->Rs;
+    a.weight_reduction = p->weight_reduction;
+    HIP_TRY(init ? launch_pf_init(a, (hipStream_t)stream) : launch_pf_step(a, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
+    return pf_call(p, b, device, stream, true);
+}
+
+int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
+    return pf_call(p, b, device, stream, false);
 }
 
 }  // extern "C"

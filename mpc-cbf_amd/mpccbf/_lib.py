@@ -24,7 +24,7 @@ EXPORTED = [
     "mpccbf_connectivity_control_solve", "mpccbf_host_operators", "mpccbf_host_last_error",
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
     "mpccbf_set_active_store", "mpccbf_cap_audit_run", "mpccbf_set_connectivity",
-    "mpccbf_host_launch_plan",
+    "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step",
 ]
 
 # active-set store (mpccbf_set_active_store): int32 words per record, side keys per record
@@ -246,6 +246,9 @@ def load():
     L.mpccbf_fov_rows_eval.argtypes = [C.c_int32, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     L.mpccbf_status_string.restype = C.c_char_p
     L.mpccbf_status_string.argtypes = [C.c_int32]
+    for f in ("mpccbf_pf_init", "mpccbf_pf_step"):
+        # (PfParams / PfBatch are defined below; resolved at call time)
+        getattr(L, f).argtypes = [C.POINTER(PfParams), C.POINTER(PfBatch), C.c_int32, vp]
     _lib = L
     return L
 
@@ -730,6 +733,80 @@ def fov_control_solve(cfg: dict, states, desired_u, nb_row_ptr, nb_xy, u, status
                         status=_ptr(status), obj=_ptr(obj), iters=_ptr(iters), nb_cov=_ptr(nb_cov))
     p = fov_control_params(cfg)
     _check(load().mpccbf_fov_control_solve(C.byref(p), C.byref(b), device, _stream(stream)))
+
+
+class PfParams(C.Structure):
+    _fields_ = [("num_particles", C.c_int32), ("init_cov", C.c_double * 3), ("process", C.c_double * 4),
+                ("meas_cov", C.c_double * 3), ("dt", C.c_double), ("fov", C.c_double), ("Rs", C.c_double),
+                ("weight_reduction", C.c_double), ("seed", C.c_uint64)]
+
+
+class PfBatch(C.Structure):
+    _fields_ = [("num_states", C.c_int32), ("states", C.c_void_p), ("agent_first", C.c_int32),
+                ("num_agents", C.c_int32), ("nb_row_ptr", C.c_void_p), ("nb_col", C.c_void_p),
+                ("num_pairs", C.c_int32), ("input", C.c_void_p), ("init_xy", C.c_void_p),
+                ("particles", C.c_void_p), ("weights", C.c_void_p), ("est_xy", C.c_void_p),
+                ("est_cov", C.c_void_p), ("flags", C.c_void_p), ("ancestors", C.c_void_p),
+                ("step_index", C.c_int64)]
+
+
+def pf_params(cfg: dict, seed: int = 0) -> PfParams:
+    """Particle-filter parameters from a config dict: fov_beta / fov_Rs and the optional keys
+    pf_num_particles, pf_init_cov, pf_process, pf_meas_cov ((cxx, cxy, cyy) / row-major 2 x 2 W),
+    pf_dt, pf_weight_reduction. Defaults: CBFControl_example.cpp:96-99 (100 particles, 1.0 I,
+    0.25 I, 0.05 I), the filter's dt 0.2 (particle_filter.cpp:19) and a reduction of 10."""
+    p = PfParams()
+    p.num_particles = int(cfg.get("pf_num_particles", 100))
+    for name, key, default in (("init_cov", "pf_init_cov", (1.0, 0.0, 1.0)),
+                               ("process", "pf_process", (0.25, 0.0, 0.0, 0.25)),
+                               ("meas_cov", "pf_meas_cov", (0.05, 0.0, 0.05))):
+        arr = getattr(p, name)
+        vals = cfg.get(key, default)
+        if len(vals) != len(arr):
+            raise ValueError(f"{key} needs {len(arr)} entries")
+        for i, v in enumerate(vals):
+            arr[i] = float(v)
+    p.dt = float(cfg.get("pf_dt", 0.2))
+    p.fov, p.Rs = float(cfg["fov_beta"]), float(cfg["fov_Rs"])
+    p.weight_reduction = float(cfg.get("pf_weight_reduction", 10.0))
+    p.seed = int(seed) & ((1 << 64) - 1)
+    return p
+
+
+def _pf_call(fn_name, params, states, nb_row_ptr, nb_col, num_pairs, particles, weights, est_xy, est_cov,
+             agent_first, num_agents, input, init_xy, flags, ancestors, step_index, device, stream):
+    fn = getattr(load(), fn_name)
+    if num_agents is None:
+        num_agents = states.shape[0] - agent_first
+    b = PfBatch(num_states=states.shape[0], states=_ptr(states), agent_first=int(agent_first),
+                num_agents=int(num_agents), nb_row_ptr=_ptr(nb_row_ptr), nb_col=_ptr(nb_col),
+                num_pairs=int(num_pairs), input=_ptr(input), init_xy=_ptr(init_xy),
+                particles=_ptr(particles), weights=_ptr(weights), est_xy=_ptr(est_xy),
+                est_cov=_ptr(est_cov), flags=_ptr(flags), ancestors=_ptr(ancestors),
+                step_index=int(step_index))
+    _check(fn(C.byref(params), C.byref(b), int(device), _stream(stream)))
+
+
+def pf_init(params: PfParams, states, nb_row_ptr, nb_col, num_pairs, particles, weights, est_xy, est_cov,
+            agent_first=0, num_agents=None, init_xy=None, flags=None, step_index=0, device: int = 0,
+            stream=None):
+    """Batched ParticleFilter::init (mpccbf_pf_init): one filter per CSR entry of nb_row_ptr / nb_col
+    (device tensors; observer agent_first + i holds the pairs nb_row_ptr[i] .. nb_row_ptr[i+1]-1, which
+    index particles (pairs x 2 x P), weights (pairs x P), est_xy (pairs x 2), est_cov (pairs x 3) and
+    flags); num_pairs = the pairs of this call (host integer)."""
+    _pf_call("mpccbf_pf_init", params, states, nb_row_ptr, nb_col, num_pairs, particles, weights, est_xy,
+             est_cov, agent_first, num_agents, None, init_xy, flags, None, step_index, device, stream)
+
+
+def pf_step(params: PfParams, states, nb_row_ptr, nb_col, num_pairs, particles, weights, est_xy, est_cov,
+            agent_first=0, num_agents=None, input=None, flags=None, ancestors=None, step_index=0,
+            device: int = 0, stream=None):
+    """Batched PFApplications::processFovUpdate (mpccbf_pf_step): predict, negative information,
+    measurement update of the visible neighbours, resampling, estimate; arguments as pf_init, input
+    (pairs x 2) the optional per-pair motion input, ancestors (pairs x P int32) the resampling's
+    choices. est_xy / est_cov have the row formats of fov_control_solve's nb_xy / nb_cov."""
+    _pf_call("mpccbf_pf_step", params, states, nb_row_ptr, nb_col, num_pairs, particles, weights, est_xy,
+             est_cov, agent_first, num_agents, input, None, flags, ancestors, step_index, device, stream)
 
 
 def fov_rows_eval(ego, nb_xy, fov: float, Ds: float, Rs: float, bbox=(0.0, 0.0, 0.0), stream=None):

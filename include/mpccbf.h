@@ -311,6 +311,11 @@ int mpccbf_run_steps(mpccbf_ctx* ctx, const mpccbf_batch* batch, mpccbf_run* run
 int mpccbf_set_variant(mpccbf_ctx* ctx, int variant);
 /* Name of the IMPC kernel instantiation the current variant launches (diagnostics). */
 const char* mpccbf_kernel_name(const mpccbf_ctx* ctx);
+/* Launch form of the context's last IMPC main launch (diagnostics; a static string): "loop" when it
+ * ran the instantiation specialised on the closed-loop launch's options — mpccbf_run_steps in grid
+ * mode with targets, traj_t, x, obj and the status / iteration logs or buffers, and none of
+ * substeps, cov, nb_out, primal_res, dual_res — else "generic". Same kernel name, same results. */
+const char* mpccbf_launch_form(const mpccbf_ctx* ctx);
 
 /* Active-set store (feature macro; MPCCBF_ABI_VERSION is unchanged: no struct changed layout).
  *
@@ -726,6 +731,18 @@ typedef struct mpccbf_host_plan {
 int mpccbf_host_launch_plan(const mpccbf_params* p, const mpccbf_options* opt, int32_t variant,
                             int32_t num_agents, int32_t csr, int32_t knn_k, int32_t store,
                             int32_t connectivity, int32_t wide_max, mpccbf_host_plan* out);
+/* The same plan's main launch with the launch-uniform options given (bit i of `facts` set: option i
+ * of MPCCBF_FACT_* is given / on): its kernel id (the library's ImpcKernel), name and launch form
+ * ("generic", "loop"; static strings). Any pointer may be NULL. */
+enum {
+    MPCCBF_FACT_TARGETS = 0, MPCCBF_FACT_TRAJ_T, MPCCBF_FACT_SUBSTEPS, MPCCBF_FACT_COV, MPCCBF_FACT_NB_OUT,
+    MPCCBF_FACT_PRIMAL_RES, MPCCBF_FACT_DUAL_RES, MPCCBF_FACT_CONE, MPCCBF_FACT_X, MPCCBF_FACT_STATUS,
+    MPCCBF_FACT_OBJ, MPCCBF_FACT_ITERS, MPCCBF_FACT_NEXT_STATES, MPCCBF_FACT_INSERT, MPCCBF_FACT_COUNT
+};
+int mpccbf_host_launch_form(const mpccbf_params* p, const mpccbf_options* opt, int32_t variant,
+                            int32_t num_agents, int32_t csr, int32_t knn_k, int32_t store,
+                            int32_t connectivity, int32_t wide_max, uint32_t facts, int32_t* kernel_id,
+                            const char** kernel_name, const char** form);
 
 /* Diagnostics */
 const char* mpccbf_last_error(void);

@@ -92,6 +92,7 @@ struct mpccbf_ctx {
     // grid's knn_k nearest)
     bool last_csr = false;
     int last_knn = 0;
+    mpccbf::LaunchForm last_form = mpccbf::FORM_GENERIC;  // its launch form (mpccbf_launch_form)
     // active-set store (mpccbf_set_active_store): the caller's device buffer of store_rows records,
     // or nullptr; store_min_steps as the kernels take it (>= 1, or < 0: export only)
     int32_t* store = nullptr;
@@ -210,7 +211,6 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr ends at row " +
                                                      std::to_string(c->conn.team_ptr.back()) + " > num_states (" +
                                                      std::to_string(b->num_states) + ")");
-    const LaunchPlan plan = impc_launch_plan(ops, c->variant, b->num_agents, !grid, b->knn_k, store != nullptr, conn);
     ImpcArgs a;
     std::memset(&a, 0, sizeof(a));
     HIP_TRY(hipSetDevice(c->device));
@@ -297,6 +297,24 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     a.substeps = b->substeps;
     a.nb_out = b->nb_out;
     a.kclock = kclock;
+    // the launch-uniform options, as the arguments just filled hold them (the plan's loop form)
+    LaunchFacts lf{};
+    lf.targets = a.targets != nullptr;
+    lf.traj_t = a.traj_t != nullptr;
+    lf.substeps = a.substeps != nullptr;
+    lf.cov = a.cov != nullptr;
+    lf.nb_out = a.nb_out != nullptr;
+    lf.primal_res = a.primal_res != nullptr;
+    lf.dual_res = a.dual_res != nullptr;
+    lf.cone = a.grid.cone > 0.0;
+    lf.x = a.x != nullptr;
+    lf.status = a.status != nullptr;
+    lf.obj = a.obj != nullptr;
+    lf.iters = a.iters != nullptr;
+    lf.next_states = a.next_states != nullptr;
+    lf.insert = a.grid.ins_cnt != nullptr;
+    const LaunchPlan plan =
+        impc_launch_plan(ops, c->variant, b->num_agents, !grid, b->knn_k, store != nullptr, conn, lf);
     if (b->substeps && !b->traj_t)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "substeps (closed-loop records) needs traj_t");
     // fallback launch: agents the main launch defers (the lean launch: QPs that need the PDIP or
@@ -313,6 +331,7 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     c->last_n = b->num_agents;
     c->last_csr = !grid;
     c->last_knn = b->knn_k;
+    c->last_form = plan.form;
     if (fb && c->defer_cap < b->num_agents) {
         const size_t bytes = 2 * (size_t)(b->num_agents + 2) * sizeof(int32_t);
         c->defer_cap = 0;
@@ -444,6 +463,8 @@ int32_t mpccbf_impc_launch_waves(const mpccbf_ctx* c, int32_t num_agents) {
 const char* mpccbf_kernel_name(const mpccbf_ctx* c) {
     return c ? ctx_plan(c, c->last_n, c->last_csr, c->last_knn, c->store != nullptr).name : "";
 }
+
+const char* mpccbf_launch_form(const mpccbf_ctx* c) { return launch_form_name(c ? c->last_form : FORM_GENERIC); }
 
 int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t min_steps) {
     if (rows < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows must be >= 0");

@@ -218,4 +218,24 @@ __host__ __device__ inline int as_cbf_key(int nb, int sample) { return -(1 + nb 
 
 constexpr int NSTAMP = 8;
 
+// Launch form of the separable agent (impc_sep_agent and the shared steps it reaches): what the code
+// knows at compile time about the options that are the same for every agent of a launch.
+//   FORM_GENERIC — nothing: every option is a run-time test of ImpcArgs (any caller, any batch);
+//   FORM_LOOP    — the closed-loop launch of mpccbf_run_steps in grid mode as the benchmark drives
+//                  it: grid query without a cone, targets, traj_t, x / status / obj / iters /
+//                  next_states and the next step's table present; no substeps, cov, nb_out,
+//                  primal_res, dual_res. The other side of each test is not compiled.
+// impc_launch_plan alone decides which launch qualifies (LaunchFacts, launch_plan.hpp). kclock stays
+// a run-time test in both forms, and so does stamps in the diagnostics builds.
+enum LaunchForm : int { FORM_GENERIC = 0, FORM_LOOP = 1 };
+
+// A form as a type: `loop` folds each launch-uniform test where it stands — an option the loop form
+// has is tested as (LF::loop || args.x), one it lacks as (!LF::loop && args.nb_out) — so the generic
+// form's tests are the plain run-time ones, expression for expression, and the loop form compiles
+// neither the test nor its other side.
+template <int FORM>
+struct FormOf {
+    static constexpr bool loop = FORM == FORM_LOOP;
+};
+
 }  // namespace mpccbf

@@ -66,7 +66,7 @@ __device__ __forceinline__ bool nb_before(double da, int ja, double db, int jb) 
 // first k go back to the lanes by rank (through sc's first NB_MAX entries). Leaves the k nearest
 // in sc.idx / sc.cst[.] positions 0 .. nk-1 sorted by agent index (sc.src[p] = p); returns nk.
 // G = 64: the four rows of the wave run the same query redundantly.
-template <int G>
+template <int G, int FORM = FORM_GENERIC>
 __device__ __forceinline__ int grid_neighbors_stream(const ImpcArgs& args, int self, double px, double py,
                                                   NbScratch& sc, int gl, double yaw, const uint32_t (&hs)[9],
                                                   const uint32_t (&nc)[9], const uint32_t (&off)[9], uint32_t total,
@@ -102,7 +102,7 @@ __device__ __forceinline__ int grid_neighbors_stream(const ImpcArgs& args, int s
             const double ey = ny - py;
             const double dd = ex * ex + ey * ey;
             keep = (j != self) && (dd <= r2);
-            if (keep && gr.cone > 0.0) {  // inside the field of view (strict)
+            if (!FormOf<FORM>::loop && keep && gr.cone > 0.0) {  // inside the field of view (strict)
                 double offa = atan2(ey, ex) - yaw;
                 offa -= 6.283185307179586 * rint(offa * 0.15915494309189535);
                 keep = fabs(offa) < gr.cone;
@@ -267,7 +267,7 @@ __device__ __forceinline__ void gq_states(const ImpcArgs& args, GridQuery<G>& q,
 // within the radius are gathered and ranked at once; beyond, grid_neighbors_stream re-runs the
 // query without a cap. Distance-only test: agents of a colliding cell that share a bucket are
 // still filtered by distance.
-template <int G>
+template <int G, int FORM = FORM_GENERIC>
 __device__ int grid_neighbors_finish(const ImpcArgs& args, int self, double px, double py, NbScratch& sc,
                                      int gl, double yaw, GridQuery<G>& q) {
     const GridArgs& gr = args.grid;
@@ -281,7 +281,7 @@ __device__ int grid_neighbors_finish(const ImpcArgs& args, int self, double px, 
         const double ey = ny - py;
         d2 = ex * ex + ey * ey;
         bool keep = j >= 0 && (j != self) && (d2 <= r2);
-        if (keep && gr.cone > 0.0) {  // inside the field of view (strict)
+        if (!FormOf<FORM>::loop && keep && gr.cone > 0.0) {  // inside the field of view (strict)
             double offa = atan2(ey, ex) - yaw;
             offa -= 6.283185307179586 * rint(offa * 0.15915494309189535);
             keep = fabs(offa) < gr.cone;
@@ -337,7 +337,7 @@ __device__ int grid_neighbors_finish(const ImpcArgs& args, int self, double px, 
         }
     }
     if (cnt > NB_CAP)
-        return grid_neighbors_stream<G>(args, self, px, py, sc, gl, yaw, q.hs, q.nc, q.off, total, q.full);
+        return grid_neighbors_stream<G, FORM>(args, self, px, py, sc, gl, yaw, q.hs, q.nc, q.off, total, q.full);
     wave_lds_sync();
     // rank by (d2, index): keep the k nearest
     const int k = gr.k;
@@ -511,11 +511,20 @@ __device__ __forceinline__ void agent_linear_term(const DevOps& op, const double
 // tail) the objective constant's terms, summed over the group. Every operator entry is a vector
 // load issued at once (the one-lane form serialised ~12 scalar-cache round trips). Returns this
 // lane's q_i (0 beyond NZ) and the constant (every lane).
-template <int NZ, int G>
+template <int NZ, int G, int FORM = FORM_GENERIC>
 __device__ __forceinline__ double agent_linear_term_lanes(const DevOps& op, const double* buf,
-                                                          const ImpcArgs& args, int ai, const double (&s0)[6],
+                                                          const ImpcArgs& args, int ai, const double (&s0in)[6],
                                                           int gl, double& kconst) {
     static_assert(NZ <= G && G >= 9, "one lane per linear-term entry");
+    // (the loop form works on a copy of the state: with the one branch it keeps, the lane's entry
+    // s0s below otherwise becomes one indexed load from the caller's array, which then lives in
+    // scratch instead of registers; the generic form reads the caller's array as ever)
+    double s0copy[6];
+    if constexpr (FormOf<FORM>::loop) {
+#pragma unroll
+        for (int s = 0; s < 6; s++) s0copy[s] = s0in[s];
+    }
+    const double (&s0)[6] = *(FormOf<FORM>::loop ? (const double (*)[6])&s0copy : &s0in);
     const int i = gl < NZ ? gl : 0;
     // constant: s0^T Ks s0 + t^T Kt s0 — lane s < 6: s0_s (Ks s0)_s; lane 6 + d: t_d (Kt s0)_d
     const int sr = gl < 6 ? gl : 0;
@@ -523,7 +532,7 @@ __device__ __forceinline__ double agent_linear_term_lanes(const DevOps& op, cons
     double s0s = s0[0];
 #pragma unroll
     for (int k = 1; k < 6; k++) s0s = sr == k ? s0[k] : s0s;
-    if (args.targets) {
+    if (FormOf<FORM>::loop || args.targets) {
         // every load first (a scheduling barrier keeps them ahead of the arithmetic: interleaved,
         // each group of loads waited for the previous one)
         double qs[6], qt[3], t[3], kr[6];
@@ -653,7 +662,7 @@ __device__ __forceinline__ void cbf_ego_state(const DevOps& op, const double* bu
 // when a single row already excludes every acceleration in the box.
 // TAG (the active-set store's instantiations): tags[slot] = the staged row's key, as_cbf_key
 // (neighbour's state index, sample); tags is LDS, written through an LDS-typed pointer.
-template <int NZ, int G, bool TAG = false>
+template <int NZ, int G, bool TAG = false, int FORM = FORM_GENERIC>
 __device__ int stage_cbf_rows(const DevOps& op, const double* buf, const ImpcArgs& args, int it,
                               const double (&s0)[6], const double (&y)[NZ], bool grid_mode,
                               const NbScratch* nbs, int nb0, int nnb, double* stage, int cap, int gl,
@@ -683,7 +692,7 @@ __device__ int stage_cbf_rows(const DevOps& op, const double* buf, const ImpcArg
             double a[3] = {0.0, 0.0, 0.0}, b = 0.0;
             if (j < nnb) {
                 double npx, npy, nvx, nvy;
-                if (grid_mode) {  // read by the neighbour query (LDS)
+                if (FormOf<FORM>::loop || grid_mode) {  // read by the neighbour query (LDS)
                     const int c = nbs->src[j];
                     npx = nbs->cst[0][c];
                     npy = nbs->cst[1][c];
@@ -739,7 +748,7 @@ __device__ int stage_cbf_rows(const DevOps& op, const double* buf, const ImpcArg
 // time: lane 6 k + s the state, lane 18 + 3 k + d the U_k s0 term, 27 doubles) with the same
 // arithmetic as cbf_ego_state, and the pairs go in the same sample-major order: the staged rows
 // are bit-identical to stage_cbf_rows'.
-template <int NZ, bool TAG = false>
+template <int NZ, bool TAG = false, int FORM = FORM_GENERIC>
 __device__ int stage_cbf_rows_pairs(const DevOps& op, const double* buf, const ImpcArgs& args, int it,
                                     const double (&s0)[6], const double (&y)[NZ], bool grid_mode,
                                     const NbScratch* nbs, int nb0, int nnb, double* stage, int cap, int gl,
@@ -794,7 +803,7 @@ __device__ int stage_cbf_rows_pairs(const DevOps& op, const double* buf, const I
 #pragma unroll
                 for (int sr = 0; sr < 6; sr++) e[sr] = smp[6 * kk + sr];
                 double npx, npy, nvx, nvy;
-                if (grid_mode) {
+                if (FormOf<FORM>::loop || grid_mode) {
                     const int c = nbs->src[j];
                     npx = nbs->cst[0][c];
                     npy = nbs->cst[1][c];
@@ -881,8 +890,9 @@ __device__ __forceinline__ double normal_sample(uint64_t seed, int64_t step, int
 // The closed-loop noise draws of the kept curve's next state (normal_sample(..., comp, 0), comp =
 // lane < 6), formed at the start of the agent (they depend on the seed, step and agent alone: the
 // transcendental chain overlaps the setup's loads instead of closing the agent) into noise0[0..6)
+template <int FORM = FORM_GENERIC>
 __device__ __forceinline__ void early_noise(const ImpcArgs& args, int ai, int gl, double* noise0) {
-    if (args.traj_t == nullptr || gl >= 6) return;
+    if ((!FormOf<FORM>::loop && args.traj_t == nullptr) || gl >= 6) return;
     const double sd = gl < 3 ? args.pos_std : args.vel_std;
     if (sd > 0.0) noise0[gl] = normal_sample(args.noise_seed, args.step_index, args.agent_first + ai, gl);
 }
@@ -953,18 +963,19 @@ __device__ __forceinline__ double curve_component_any(const DevOps& op, const do
 // FIXED: the curve evaluation's compile-time control-point count (C = 4) when it applies (off for the
 // FoV slack kernel, whose registers it pushes into scratch); AZE: a fresh curve's next state from the
 // AZ / AS rows when DevOps::az_at_eval (off in the FoV kernels, where it costs scratch)
-template <int NZ, int G, bool FIXED = true, bool AZE = true>
+template <int NZ, int G, bool FIXED = true, bool AZE = true, int FORM = FORM_GENERIC>
 __device__ __forceinline__ void write_agent_outputs(const DevOps& op, const double* buf,
                                                     const ImpcArgs& args, int ai, int gl,
                                                     const double (&s0)[6], const double (&yk)[NZ],
                                                     bool have_curve, const double* noise0 = nullptr) {
-    const bool sim = args.traj_t != nullptr;
+    using LF = FormOf<FORM>;
+    const bool sim = LF::loop || args.traj_t != nullptr;
     const double t_stored = sim ? args.traj_t[ai] : 0.0;  // (loaded here: in flight during the x rows)
     // this step's control points x = Xs s0 + Z y to args.x, XU rows per lane at a time (their loads
     // in flight together; one row at a time, each row's loads waited for the previous row's)
     // (staging them in LDS for the curve evaluation below, with its piece lookup from the kernel
     // arguments, measured slower: 0.15 us per agent)
-    const bool want_x = args.x && (have_curve || !sim);
+    const bool want_x = (LF::loop || args.x) && (have_curve || !sim);
     if (want_x && !have_curve) {
         for (int i = gl; i < op.n; i += G) args.x[(size_t)ai * op.n + i] = __builtin_nan("");
     } else if (want_x) {
@@ -1013,7 +1024,7 @@ __device__ __forceinline__ void write_agent_outputs(const DevOps& op, const doub
             } else {
                 v = curve_component_any<NZ, FIXED>(op, buf, xr, s0, yk, t_new, gl);
             }
-            if (args.substeps) {  // sub-steps 1 .. nsub - 1: the curve at t_prev + Ts k, own draws
+            if (!LF::loop && args.substeps) {  // sub-steps 1 .. nsub - 1: the curve at t_prev + Ts k, own draws
                 for (int k = 1; k < op.nsub; k++) {
                     double u = curve_component_any<NZ, FIXED>(op, buf, xr, s0, yk, fmin(t_prev + op.Ts * k, tmax), gl);
                     if (sd > 0.0) u = fma(sd, normal_sample(args.noise_seed, args.step_index, agent, gl, op.nsub - k), u);
@@ -1033,7 +1044,7 @@ __device__ __forceinline__ void write_agent_outputs(const DevOps& op, const doub
             for (int k = 1; k <= op.nsub; k++) {
                 const double n = sd > 0.0 ? sd * normal_sample(args.noise_seed, args.step_index, agent, gl, op.nsub - k) : 0.0;
                 p = gl < 3 ? p + n : n;
-                if (args.substeps && k < op.nsub) args.substeps[((size_t)ai * op.nsub + k - 1) * 6 + gl] = p;
+                if (!LF::loop && args.substeps && k < op.nsub) args.substeps[((size_t)ai * op.nsub + k - 1) * 6 + gl] = p;
             }
             v = p;
         }
@@ -1053,9 +1064,9 @@ __device__ __forceinline__ void write_agent_outputs(const DevOps& op, const doub
         }
         if (sd > 0.0) v = fma(sd, normal_sample(args.noise_seed, args.step_index, agent, gl), v);
     }
-    if (args.substeps) args.substeps[((size_t)ai * op.nsub + op.nsub - 1) * 6 + gl] = v;
-    if (args.next_states) args.next_states[(size_t)ai * 6 + gl] = v;
-    if (args.grid.ins_cnt) {  // the next step's neighbour table gets this row (lanes 0, 1, 3, 4)
+    if (!LF::loop && args.substeps) args.substeps[((size_t)ai * op.nsub + op.nsub - 1) * 6 + gl] = v;
+    if (LF::loop || args.next_states) args.next_states[(size_t)ai * 6 + gl] = v;
+    if (LF::loop || args.grid.ins_cnt) {  // the next step's neighbour table gets this row (lanes 0, 1, 3, 4)
         const int base = (int)(threadIdx.x & 63u) & ~(G - 1);
         const double y = __shfl(v, base + 1, 64), vx = __shfl(v, base + 3, 64), vy = __shfl(v, base + 4, 64);
         if (gl == 0) grid_insert(args.grid, v, y, vx, vy, (uint32_t)(args.agent_first + ai));
@@ -1131,12 +1142,13 @@ __device__ __forceinline__ void stamp(const ImpcArgs& args, int ai, int gl, int 
 
 // diagnostics (args.nb_out): the first 16 entries of the agent's neighbour list as the kernel built
 // its rows from (grid mode: the query's result in LDS, sorted by index; CSR: the caller's list)
+template <int FORM = FORM_GENERIC>
 __device__ __forceinline__ void write_nb_out(const ImpcArgs& args, int ai, int gl, bool grid_mode,
                                              const NbScratch& nbs, int nb0, int nnb) {
-    if (!args.nb_out || gl >= 16) return;
+    if (FormOf<FORM>::loop || !args.nb_out || gl >= 16) return;
     int v = -1;
     if (gl < nnb) {
-        if (grid_mode) {
+        if (FormOf<FORM>::loop || grid_mode) {
             v = nbs.idx[gl];
         } else {
             v = args.nb_col[nb0 + gl];
@@ -1146,15 +1158,17 @@ __device__ __forceinline__ void write_nb_out(const ImpcArgs& args, int ai, int g
     args.nb_out[(size_t)ai * 16 + gl] = v;
 }
 
+template <int FORM = FORM_GENERIC>
 __device__ __forceinline__ void write_iteration(const ImpcArgs& args, size_t oi, int gl, int st,
                                                 double obj, int iters,
                                                 double prs = __builtin_nan(""), double drs = __builtin_nan("")) {
+    using LF = FormOf<FORM>;
     if (gl == 0) {
-        if (args.status) args.status[oi] = st;
-        if (args.obj) args.obj[oi] = obj;
-        if (args.iters) args.iters[oi] = iters;
-        if (args.primal_res) args.primal_res[oi] = prs;
-        if (args.dual_res) args.dual_res[oi] = drs;
+        if (LF::loop || args.status) args.status[oi] = st;
+        if (LF::loop || args.obj) args.obj[oi] = obj;
+        if (LF::loop || args.iters) args.iters[oi] = iters;
+        if (!LF::loop && args.primal_res) args.primal_res[oi] = prs;
+        if (!LF::loop && args.dual_res) args.dual_res[oi] = drs;
     }
 }
 

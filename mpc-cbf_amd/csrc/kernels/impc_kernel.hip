@@ -81,6 +81,8 @@ hipError_t launch_impc(ImpcKernel k, int blocks, int block_size, const DevOps& o
         case IMPC_DENSE_16_4: return launch_impc_dense<6, 16, 4>(blocks, block_size, op, buf, a, s);
         case IMPC_DENSE_64_1: return launch_impc_dense<6, 64, 1>(blocks, block_size, op, buf, a, s);
         case IMPC_DENSE_64_4: return launch_impc_dense<6, 64, 4>(blocks, block_size, op, buf, a, s);
+        // (the loop form of IMPC_SEP, FORM_LOOP: the closed-loop launch's options as constants)
+        case IMPC_SEP_LOOP: return go(dev::impc_sep_kernel<1, 1, false, 256, false, false, FORM_LOOP>);
         default: return hipErrorInvalidValue;
     }
 }

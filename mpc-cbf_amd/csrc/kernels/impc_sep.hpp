@@ -324,8 +324,11 @@ __device__ __forceinline__ SepRows<SB, CB>& pick_rows(SepRows<SB, CB>& reg, SepR
 // but per-iteration outputs, the neighbour list and stamps has been written by then, all of which the
 // full pipeline's run from scratch rewrites with the same values. (A flag, not a return value: the
 // other instantiations' code stays what it was, tools/code_sizes.py.)
+// FORM (LaunchForm, impc.hpp; the loop form only for the handing-over lean pipeline): what is known
+// at compile time about the launch-uniform options. Only the tests change with it: every
+// expression on a path the form keeps is the generic form's.
 template <int SB, int CB, bool SLACK, bool QUEUE, bool LEAN = false, bool STORE = false, bool CONN = false,
-          bool HANDOVER = false>
+          bool HANDOVER = false, int FORM = FORM_GENERIC>
 __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* __restrict__ buf, const ImpcArgs& args,
                                const int ai, const int gl, double* stage, double* red, NbScratch& nbs,
                                double* keep, SepRowsLds<SB, CB>* rows_lds = nullptr, double* bconst = nullptr,
@@ -334,6 +337,8 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     static_assert(!(STORE && SLACK), "the active-set store is not built for slack mode");
     static_assert(!CONN || (!SLACK && !STORE && !LEAN), "connectivity rows: the full non-slack pipeline");
     static_assert(!HANDOVER || (LEAN && !STORE), "only the lean pipeline hands an agent over");
+    static_assert(FORM == FORM_GENERIC || (HANDOVER && !SLACK && !QUEUE), "the loop form: the main launch's lean agent");
+    using LF = FormOf<FORM>;
     constexpr int G = 16;
     constexpr int NZ = SEP_NZ;
     constexpr int cap = CB * G;  // CBF rows per agent
@@ -349,9 +354,9 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     for (int i = 0; i < 6; i++) s0[i] = args.states[(size_t)self * 6 + i];
     // the next state's noise draws, while the state is in flight (the keep area's last 6 doubles)
     double* const noise0 = keep + sep_keep_doubles<SB, SLACK, LEAN>() - 6;
-    early_noise(args, ai, gl, noise0);
+    early_noise<FORM>(args, ai, gl, noise0);
     // grid mode: the neighbour query's loads are staged between the setup's (gq_*)
-    const bool grid_mode = args.nb_row_ptr == nullptr;
+    const bool grid_mode = LF::loop || args.nb_row_ptr == nullptr;
     GridQuery<G> gq;
     // (the state arrives before the branch: waited for only on one side, the join would wait for
     // every load in flight, the query's included)
@@ -370,7 +375,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     double* qk = keep + 16 * (SEP_NZ + (LEAN ? 0 : 2 * SEP_D * SB)) + 8 + (SLACK ? 0 : POL_K + 1);
     {
         double kc0;
-        const double q0 = agent_linear_term_lanes<NZ, G>(op, buf, args, ai, s0, gl, kc0);
+        const double q0 = agent_linear_term_lanes<NZ, G, FORM>(op, buf, args, ai, s0, gl, kc0);
         if (gl < NZ) qk[gl] = q0;
         if (gl == 0) {
             qk[NZ] = kc0;
@@ -422,9 +427,9 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
         nb0 = args.nb_row_ptr[ai];
         nnb = args.nb_row_ptr[ai + 1] - nb0;
     } else {
-        nnb = grid_neighbors_finish<G>(args, self, s0[0], s0[1], nbs, gl, 0.0, gq);
+        nnb = grid_neighbors_finish<G, FORM>(args, self, s0[0], s0[1], nbs, gl, 0.0, gq);
     }
-    write_nb_out(args, ai, gl, grid_mode, nbs, nb0, nnb);
+    write_nb_out<FORM>(args, ai, gl, grid_mode, nbs, nb0, nnb);
     if (SLACK && !QUEUE && nnb > G && args.defer) {  // slack mode: beyond one lane per neighbour
         defer_agent(args, agent(), gl);
         return;
@@ -496,7 +501,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
     for (int it = 0; it < op.impc_iter; it++) {
         const size_t oi = (size_t)agent() * op.impc_iter + it;
         if (!success) {
-            write_iteration(args, oi, gl, ST_UNKNOWN, __builtin_nan(""), 0);
+            write_iteration<FORM>(args, oi, gl, ST_UNKNOWN, __builtin_nan(""), 0);
             continue;
         }
         bool row_infeasible = false;
@@ -527,10 +532,10 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             constexpr int STG = CB * 16 * (SEP_NZ + 1) > sep_pol_doubles<SB, CB>() ? CB * 16 * (SEP_NZ + 1)
                                                                                    : sep_pol_doubles<SB, CB>();
             if (STG - cap * (NZ + 1) >= 27 && it > 0)
-                count = stage_cbf_rows_pairs<NZ, STORE>(op, buf, args, it, sx, y, grid_mode, &nbs, nb0, nnb, stage, cap,
+                count = stage_cbf_rows_pairs<NZ, STORE, FORM>(op, buf, args, it, sx, y, grid_mode, &nbs, nb0, nnb, stage, cap,
                                                         gl, &row_infeasible, stage + cap * (NZ + 1), astore);
             else
-                count = stage_cbf_rows<NZ, G, STORE>(op, buf, args, it, sx, y, grid_mode, &nbs,
+                count = stage_cbf_rows<NZ, G, STORE, FORM>(op, buf, args, it, sx, y, grid_mode, &nbs,
                                                      nb0, nnb, stage, cap, gl, &row_infeasible, astore);
             if constexpr (CONN)
                 count = stage_conn_rows<NZ>(op, buf, args, conn, args.agent_first + agent(), it, sx, y,
@@ -607,7 +612,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             double tl = 0.0, prs = __builtin_nan(""), drs = __builtin_nan("");
             const int k0 = warm_count(it);
             const int r = sep_dual_as<G, SB, CB>(rw, live, opp(buf, op.o_Pr), Pi, q, yu, op.tol, op.dual_as, stage, y,
-                                                 prs, drs, nit, nullptr, HANDOVER ? args.dual_res != nullptr : true, tl,
+                                                 prs, drs, nit, nullptr, HANDOVER ? !LF::loop && args.dual_res != nullptr : true, tl,
                                                  nullptr, k0, act,
                                                  (STORE || it == 0) ? act : nullptr, nullptr, bsc, bw);
             if (r > 0) {
@@ -780,7 +785,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
             success = false;
         }
         SSTAMP(20);
-        write_iteration(args, oi, gl, st, objv, nit, res[0], res[1]);
+        write_iteration<FORM>(args, oi, gl, st, objv, nit, res[0], res[1]);
         SSTAMP(21);
         if (it == 0) steps0 = nit;
         if (it < 2) stamp(args, ai, gl, 4 + 2 * it);
@@ -791,7 +796,7 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
 #pragma unroll
     for (int i = 0; i < NZ; i++) yk[i] = ykeep[16 * i];
     load_state_lds(s0k, sx);
-    write_agent_outputs<NZ, G>(op, buf, args, agent(), gl, sx, yk, have_curve, noise0);
+    write_agent_outputs<NZ, G, true, true, FORM>(op, buf, args, agent(), gl, sx, yk, have_curve, noise0);
     if constexpr (STORE)
         if (gl < AS_WORDS) store.records[(size_t)(args.agent_first + agent()) * AS_WORDS + gl] = rec_out;
     stamp(args, ai, gl, 7);
@@ -840,9 +845,12 @@ static __device__ __attribute__((noinline, not_tail_called)) void impc_sep_compl
 // — inline and finishes the agents it does not settle with a call of impc_sep_complete once the
 // wave's four groups have come back: one launch, the hot path without the interior-point solver's
 // code. LEAN is the two-launch form of the same split (the unsettled agents go to the queue).
-template <int SB, int CB, bool SLACK, int BS, bool QUEUE = false, bool LEAN = false>
+// FORM (LaunchForm): the launch form of the plain main launch's lean agent; the completion it calls
+// is the generic one in either form (one function, the same call).
+template <int SB, int CB, bool SLACK, int BS, bool QUEUE = false, bool LEAN = false, int FORM = FORM_GENERIC>
 __global__ void __launch_bounds__(BS) impc_sep_kernel(const DevOps op, const double* __restrict__ buf,
                                                        const ImpcArgs args) {
+    static_assert(FORM == FORM_GENERIC || (!SLACK && !QUEUE && !LEAN), "the loop form: the plain main launch");
     constexpr int GPB = BS / 16;
     // CBF-row staging, reused as the dual active set's scratch (sep_pol_doubles)
     // (slack mode: the slack-pattern active set's scratch + its multipliers, sep_slack_patterns)
@@ -871,7 +879,7 @@ __global__ void __launch_bounds__(BS) impc_sep_kernel(const DevOps op, const dou
             // set — the PDIP-only diagnostic setting — every agent takes the completion)
             bool left = op.dual_as <= 0;
             if (!left)
-                impc_sep_agent<SB, CB, false, false, true, false, false, true>(
+                impc_sep_agent<SB, CB, false, false, true, false, false, true, FORM>(
                     op, buf, args, ai, gl, stage_all[gib], red_all[gib], nb_scratch[gib], keep_all[gib], nullptr,
                     bconst_all[gib], nullptr, StoreArgs{nullptr, 0}, ConnArgs{}, &left);
             const unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();

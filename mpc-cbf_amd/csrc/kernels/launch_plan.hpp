@@ -36,6 +36,19 @@ enum ImpcKernel : int32_t {
     IMPC_CONN,         // impc_conn.hip: impc_sep_conn_kernel<4,64> (impc_sep.hpp)
     IMPC_FOV,          // impc_fov.hip: impc_fov_kernel<false>
     IMPC_FOV_SLACK,    //   impc_fov_kernel<true>
+    IMPC_SEP_LOOP,     // impc_kernel.hip: IMPC_SEP in the loop form (FORM_LOOP, impc.hpp), reported under
+                       //   IMPC_SEP's name
+};
+
+// What is the same for every agent of one launch and known where ImpcArgs is filled (impc_enqueue):
+// the options the loop form fixes at compile time. All false (the default): no launch qualifies.
+struct LaunchFacts {
+    bool targets;      // ImpcArgs::targets (else refs)
+    bool traj_t;       // closed-loop simulator semantics
+    bool substeps, cov, nb_out, primal_res, dual_res;  // optional inputs / outputs given
+    bool cone;         // GridArgs::cone > 0
+    bool x, status, obj, iters, next_states;  // outputs given
+    bool insert;       // the launch fills the next step's neighbour table (GridArgs::ins_cnt)
 };
 
 struct LaunchPlan {
@@ -49,7 +62,9 @@ struct LaunchPlan {
     bool store;           // the launches read and write the active-set store
     bool defer;           // the main launch appends to ImpcArgs::defer; `capacity` must follow
     ImpcKernel capacity;  // the capacity launch (IMPC_QUEUE_*: its blocks), IMPC_NONE: none
+    LaunchForm form;      // the main launch's form (FORM_LOOP: IMPC_SEP_LOOP alone)
 };
+const char* launch_form_name(LaunchForm f);  // "generic", "loop"
 constexpr int IMPC_QUEUE_BLOCK = 64, IMPC_QUEUE_AGENTS = 4;
 
 // Bounds of the kernels, defined next to them: the operator prefix the one-agent-per-wave kernel
@@ -59,7 +74,10 @@ extern const int IMPC_FOV_ROWS_MAX;
 
 // Pure: no HIP runtime call, no context state. `op` as mpccbf_create packed it (a store attached
 // turns DevOps::lean off here, not in a copy); n: the agents of the launch.
-LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int knn_k, bool store, bool conn);
+// facts: the launch-uniform options; IMPC_SEP becomes IMPC_SEP_LOOP (same name, shape and clock)
+// exactly when every one of them is what the loop form fixes.
+LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int knn_k, bool store, bool conn,
+                            const LaunchFacts& facts = LaunchFacts{});
 
 inline int plan_blocks(const LaunchPlan& p, int n) { return (n + p.agents_per_block - 1) / p.agents_per_block; }
 

@@ -46,14 +46,18 @@ const KernelShape SHAPES[] = {
     {"impc_sep_conn_kernel<4,64>", 64, 4, true},
     {"impc_fov_kernel<false>", 64, 1, false},
     {"impc_fov_kernel<true>", 64, 1, false},
+    {"impc_sep_kernel<1,1,false,256>", 256, 16, true},  // (the loop form: IMPC_SEP's name)
 };
-static_assert(sizeof(SHAPES) / sizeof(SHAPES[0]) == IMPC_FOV_SLACK + 1, "one shape per ImpcKernel");
+static_assert(sizeof(SHAPES) / sizeof(SHAPES[0]) == IMPC_SEP_LOOP + 1, "one shape per ImpcKernel");
 
 constexpr int VARIANT_SEP16 = 4, VARIANT_WIDE = 5;
 
 }  // namespace
 
-LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int knn_k, bool store, bool conn) {
+const char* launch_form_name(LaunchForm f) { return f == FORM_LOOP ? "loop" : "generic"; }
+
+LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int knn_k, bool store, bool conn,
+                            const LaunchFacts& f) {
     // the separable layout with one row slot per lane and channel (up to 16 box rows per channel)
     const bool sep = op.sep && op.nzd == SEP_NZD_HOST;
     const bool sep16 = sep && op.sep_rows_per_dim <= 16;
@@ -79,8 +83,13 @@ LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int 
     // lists: at most knn_k neighbours x cbf_h samples), else the 64-lane one with 256 - m slots
     const bool dense16 = op.m < 64 && (variant == 3 || (variant == 0 && !csr && knn_k * op.cbf_h <= 64 - op.m));
 
+    // the loop form (FORM_LOOP, impc.hpp): every launch-uniform option as that form fixes it
+    const bool loop = !csr && f.targets && f.traj_t && !f.substeps && !f.cov && !f.cone && !f.nb_out &&
+                      !f.primal_res && !f.dual_res && f.x && f.status && f.obj && f.iters && f.next_states && f.insert;
+
     LaunchPlan p{};
     p.capacity = IMPC_NONE;
+    p.form = FORM_GENERIC;
     if (conn) {
         p.kernel = op.cbf_mode == 0 && !slack && sep16 ? IMPC_CONN : IMPC_NONE;
         p.name = SHAPES[IMPC_CONN].name;
@@ -110,6 +119,10 @@ LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int 
             p.capacity = p.store ? (exceed ? IMPC_QUEUE8_STORE : IMPC_QUEUE1_STORE) : (exceed ? IMPC_QUEUE8 : IMPC_QUEUE1);
         }
         if (!p.defer) p.capacity = IMPC_NONE;
+        if (p.kernel == IMPC_SEP && loop) {
+            p.kernel = IMPC_SEP_LOOP;
+            p.form = FORM_LOOP;
+        }
         p.name = SHAPES[p.kernel].name;
     }
     const KernelShape& sh = SHAPES[p.kernel != IMPC_NONE ? p.kernel : (conn ? IMPC_CONN : IMPC_NONE)];
@@ -353,6 +366,46 @@ PackedOps pack_operators(const Operators& o, const mpccbf_params& prm, const mpc
 }
 
 }  // namespace mpccbf
+
+extern "C" int mpccbf_host_launch_form(const mpccbf_params* p, const mpccbf_options* opt, int32_t variant,
+                                       int32_t num_agents, int32_t csr, int32_t knn_k, int32_t store,
+                                       int32_t connectivity, int32_t wide_max, uint32_t facts, int32_t* kernel_id,
+                                       const char** kernel_name, const char** form) {
+    using namespace mpccbf;
+    if (!p) return set_host_error(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    const std::string verr = validate_params(*p);
+    if (!verr.empty()) return set_host_error(MPCCBF_ERR_INVALID_ARGUMENT, verr);
+    mpccbf_options o;
+    if (opt) o = *opt; else std::memset(&o, 0, sizeof(o));
+    try {
+        PackedOps po = pack_operators(build_operators(*p, o.keep_redundant != 0), *p, o);
+        po.dev.wide_max = wide_max;
+        auto on = [&](int bit) { return ((facts >> bit) & 1u) != 0; };
+        LaunchFacts f{};
+        f.targets = on(MPCCBF_FACT_TARGETS);
+        f.traj_t = on(MPCCBF_FACT_TRAJ_T);
+        f.substeps = on(MPCCBF_FACT_SUBSTEPS);
+        f.cov = on(MPCCBF_FACT_COV);
+        f.nb_out = on(MPCCBF_FACT_NB_OUT);
+        f.primal_res = on(MPCCBF_FACT_PRIMAL_RES);
+        f.dual_res = on(MPCCBF_FACT_DUAL_RES);
+        f.cone = on(MPCCBF_FACT_CONE);
+        f.x = on(MPCCBF_FACT_X);
+        f.status = on(MPCCBF_FACT_STATUS);
+        f.obj = on(MPCCBF_FACT_OBJ);
+        f.iters = on(MPCCBF_FACT_ITERS);
+        f.next_states = on(MPCCBF_FACT_NEXT_STATES);
+        f.insert = on(MPCCBF_FACT_INSERT);
+        const LaunchPlan pl =
+            impc_launch_plan(po.dev, variant, num_agents, csr != 0, knn_k, store != 0, connectivity != 0, f);
+        if (kernel_id) *kernel_id = pl.kernel;
+        if (kernel_name) *kernel_name = pl.name;
+        if (form) *form = launch_form_name(pl.form);
+        return MPCCBF_OK;
+    } catch (const std::exception& e) {
+        return set_host_error(MPCCBF_ERR_INVALID_ARGUMENT, e.what());
+    }
+}
 
 extern "C" int mpccbf_host_launch_plan(const mpccbf_params* p, const mpccbf_options* opt, int32_t variant,
                                        int32_t num_agents, int32_t csr, int32_t knn_k, int32_t store,

@@ -24,8 +24,19 @@ EXPORTED = [
     "mpccbf_connectivity_control_solve", "mpccbf_host_operators", "mpccbf_host_last_error",
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
     "mpccbf_set_active_store", "mpccbf_cap_audit_run", "mpccbf_set_connectivity",
-    "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step",
+    "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step", "mpccbf_launch_form",
+    "mpccbf_host_launch_form",
 ]
+
+# ImpcKernel ids (csrc/kernels/launch_plan.hpp) of the 16-lane main launch: generic and loop form
+IMPC_SEP, IMPC_SEP_LOOP = 4, 20
+
+# the launch-uniform options of one IMPC launch, in the bit order of MPCCBF_FACT_* (mpccbf.h)
+LAUNCH_FACTS = ("targets", "traj_t", "substeps", "cov", "nb_out", "primal_res", "dual_res", "cone", "x",
+                "status", "obj", "iters", "next_states", "insert")
+# the closed-loop launch of run_steps in grid mode as bench.py drives it: the loop form's options
+LOOP_LAUNCH = dict.fromkeys(LAUNCH_FACTS, False)
+LOOP_LAUNCH.update(dict.fromkeys(("targets", "traj_t", "x", "status", "obj", "iters", "next_states", "insert"), True))
 
 # active-set store (mpccbf_set_active_store): int32 words per record, side keys per record
 ACTIVE_STORE_WORDS = 8
@@ -240,6 +251,9 @@ def load():
     L.mpccbf_comm_destroy.restype = None
     L.mpccbf_kernel_name.argtypes = [vp]
     L.mpccbf_kernel_name.restype = C.c_char_p
+    if hasattr(L, "mpccbf_launch_form"):  # (MPCCBF_LIB may name a library from before the launch forms)
+        L.mpccbf_launch_form.argtypes = [vp]
+        L.mpccbf_launch_form.restype = C.c_char_p
     L.mpccbf_impc_launch_waves.argtypes = [vp, C.c_int32]
     L.mpccbf_impc_launch_waves.restype = C.c_int32
     L.mpccbf_last_error.restype = C.c_char_p
@@ -406,6 +420,11 @@ class Context:
     @property
     def kernel_name(self) -> str:
         return load().mpccbf_kernel_name(self._h).decode()
+
+    @property
+    def launch_form(self) -> str:
+        """The last IMPC main launch's form (mpccbf_launch_form): "loop" or "generic"."""
+        return load().mpccbf_launch_form(self._h).decode()
 
     def build_neighbors(self, states, first, count, k, radius, row_ptr, col, stream=None):
         _check(load().mpccbf_build_neighbors(self._h, _ptr(states), states.shape[0], first, count,
@@ -585,11 +604,13 @@ class HostPlan(C.Structure):
 
 def host_launch_plan(cfg: dict, variant: int = 0, num_agents: int = 0, csr: bool = False, knn_k: int = 0,
                      store: bool = False, connectivity: bool = False, wide_max: int = 1024,
-                     with_buffer: bool = False, **options) -> dict:
+                     with_buffer: bool = False, launch: dict = None, **options) -> dict:
     """Host-only launch plan and operator packing (mpccbf_host_launch_plan); no GPU needed.
     options: fields of mpccbf_options (lean=1, keep_redundant=1, ...). Returns the fields of
     mpccbf_host_plan as a dict (names decoded, offsets a list; buf: the packed operators as a numpy
-    array when with_buffer)."""
+    array when with_buffer). launch: the launch-uniform options (keys of LAUNCH_FACTS -> bool, e.g.
+    LOOP_LAUNCH; default: none given) — the dict then also has the main launch's kernel_id, its
+    launch_form ("generic" / "loop") and, for that launch, kernel_name (mpccbf_host_launch_form)."""
     L = load()
     L.mpccbf_host_launch_plan.argtypes = [C.POINTER(Params), C.POINTER(Options)] + [C.c_int32] * 7 + [
         C.POINTER(HostPlan)]
@@ -607,6 +628,17 @@ def host_launch_plan(cfg: dict, variant: int = 0, num_agents: int = 0, csr: bool
     r = {f: getattr(out, f) for f, _ in HostPlan._fields_ if f not in ("offsets", "buf", "buf_capacity")}
     r.update(kernel_name=out.kernel_name.decode(), capacity_name=out.capacity_name.decode(),
              offsets=list(out.offsets), buf=buf)
+    if launch is not None:
+        unknown = set(launch) - set(LAUNCH_FACTS)
+        if unknown:
+            raise ValueError(f"unknown launch facts: {sorted(unknown)}")
+        mask = sum(1 << i for i, f in enumerate(LAUNCH_FACTS) if launch.get(f))
+        L.mpccbf_host_launch_form.argtypes = [C.POINTER(Params), C.POINTER(Options)] + [C.c_int32] * 7 + [
+            C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
+        kid, name, form = C.c_int32(), C.c_char_p(), C.c_char_p()
+        if L.mpccbf_host_launch_form(*args[:-1], mask, C.byref(kid), C.byref(name), C.byref(form)) != 0:
+            raise MpccbfError(L.mpccbf_host_last_error().decode())
+        r.update(kernel_id=kid.value, kernel_name=name.value.decode(), launch_form=form.value.decode())
     return r
 
 

@@ -5,6 +5,10 @@ and prints, over agents: start skew, per-phase durations (setup, neighbours, CBF
 outputs) as mean / p50 / p99 / max in microseconds, and the critical (latest-ending) agent.
 
     python tools/stamp_profile.py [N] [warm_steps] [variants...]
+
+LOOP=1: the warm-up and the instrumented launch go through run_steps as the benchmark's closed loop
+does (traj_t, noise, x / status / obj / iters, the next step's table): the launch the plan gives the
+loop form (FORM_LOOP); without it, impc_solve's launch (the generic form).
 """
 import os
 import sys
@@ -21,6 +25,7 @@ VARIANTS = [int(v) for v in sys.argv[3:]] or [0, 3]
 PH = ["setup", "neighbours", "cbf_rows0", "solve0", "cbf_rows1", "solve1", "outputs"]
 FOV = os.environ.get("WORKLOAD", "") == "fov"
 SLACK = os.environ.get("SLACK", "") == "1"
+LOOP = os.environ.get("LOOP", "") == "1"
 COV = None
 if FOV:
     cfg = swarm.fov_config(20, **(dict(slack_mode=1, slack_cost=1000.0, slack_decay_rate=0.9) if SLACK else {}))
@@ -40,9 +45,20 @@ if os.environ.get("RESIDUALS", "") != "1":  # as the bench: no residual outputs 
     out.pop("dual_res", None)
 if FOV and SLACK:
     COV = torch.tensor(np.tile([0.1, 0.0, 0.1], (N, 1)), device=dev)
-for _ in range(WARM):
-    ctx.impc_solve(st, targets=tg, knn_k=8, knn_radius=radius, cov=COV, **out)
-    st.copy_(out["next_states"])
+loop_kw = {}
+if LOOP:
+    traj_t = torch.full((N,), -1.0, dtype=torch.float64, device=dev)
+    out["x"].fill_(float("nan"))
+    loop_kw = dict(targets=tg, knn_k=8, knn_radius=radius, cov=COV, x=out["x"], status=out["status"], obj=out["obj"],
+                   iters=out["iters"], pos_std=0.001, vel_std=0.01, noise_seed=20251015)
+    r = ctx.run_steps(st, torch.empty_like(st), WARM, traj_t=traj_t, **loop_kw)
+    st = r["final"]
+    torch.cuda.synchronize()
+    traj_snap, x_snap = traj_t.clone(), out["x"].clone()
+else:
+    for _ in range(WARM):
+        ctx.impc_solve(st, targets=tg, knn_k=8, knn_radius=radius, cov=COV, **out)
+        st.copy_(out["next_states"])
 torch.cuda.synchronize()
 snap = st.clone()
 PDIP = os.environ.get("MPCCBF_LIB", "").find("prof") >= 0  # profiling build: in-loop stamps
@@ -56,8 +72,19 @@ for v in VARIANTS:
     stamps = torch.zeros(N * 8 + (N * 32 if PDIP else 0) + (N * 2 * 256 if TRACE else 0), dtype=torch.int64,
                          device=dev)
     for rep in range(3):  # last rep measured (warm caches)
-        ctx.impc_solve(snap, targets=tg, knn_k=8, knn_radius=radius, stamps=stamps, cov=COV, **out)
+        if LOOP:  # the same step again: the snapshot's states, curves and evaluation times
+            traj_t.copy_(traj_snap)
+            out["x"].copy_(x_snap)
+            ctx.run_steps(snap.clone(), torch.empty_like(snap), 1, traj_t=traj_t, step_index=WARM, stamps=stamps,
+                          **loop_kw)
+        else:
+            ctx.impc_solve(snap, targets=tg, knn_k=8, knn_radius=radius, stamps=stamps, cov=COV, **out)
     torch.cuda.synchronize()
+    if LOOP:
+        try:
+            print(f"variant {v}: closed-loop launch, form {ctx.launch_form}")
+        except AttributeError:  # (MPCCBF_LIB names a library from before the launch forms)
+            print(f"variant {v}: closed-loop launch")
     allst = stamps.cpu().numpy()
     s = allst[:N * 8].reshape(N, 8).astype(np.float64) * 0.01  # 10 ns ticks -> us
     if PDIP and v == 0:

@@ -652,10 +652,13 @@ typedef struct mpccbf_connectivity_control_batch {
     int32_t* status;           /* out, robots (qpcpp::SolveStatus), or NULL */
     double* obj;               /* out, ||u - u_des||^2 (+ slack cost), or NULL */
     int32_t* iters;            /* out, PDIP iterations, or NULL */
-    double* lambda2;           /* out, num_teams, or NULL */
+    double* lambda2;           /* out, num_teams, or NULL (NaN: a team of 0 or of more than 16) */
 } mpccbf_connectivity_control_batch;
 
-/* A team with more than 16 robots gets status MPCCBF_ERROR for all its robots. */
+/* A team with more than 16 robots gets status MPCCBF_ERROR (NaN u and obj, 0 iterations) for all
+ * its robots and NaN in lambda2. An empty team (team_ptr[t] == team_ptr[t+1]) has no rows, so none
+ * is written, and no spectrum: its lambda2 is NaN. A team of 1 has lambda2 = 0 and only its
+ * velocity rows. */
 int mpccbf_connectivity_control_solve(const mpccbf_connectivity_control_params* p,
                                       const mpccbf_connectivity_control_batch* b, int32_t device,
                                       void* hip_stream);

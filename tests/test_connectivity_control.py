@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from cbf_control_cases import laplacian as _laplacian
 
 KATS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_kats.json")))
 
@@ -31,19 +32,6 @@ def test_connectivity_cbf_known_answers(oracle):
         np.testing.assert_allclose(H, case["log_hessian"], atol=1e-6)
         assert abs(dbg[5] - case["log_Lfh"]) <= 1e-14
         assert abs(dbg[6] - case["log_Lf2h"]) <= 1e-14
-
-
-def _laplacian(pos, dmax):
-    n = len(pos)
-    sigma = dmax ** 4 / np.log(2.0)
-    A = np.zeros((n, n))
-    for i in range(n):
-        for j in range(n):
-            if i != j:
-                d2 = np.sum((pos[i] - pos[j]) ** 2)
-                if d2 <= dmax * dmax:
-                    A[i, j] = np.exp((dmax * dmax - d2) ** 2 / sigma) - 1
-    return np.diag(A.sum(axis=1)) - A
 
 
 def test_lambda2_matches_lapack(oracle):

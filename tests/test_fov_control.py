@@ -60,7 +60,7 @@ def test_oracle_solution_satisfies_the_fov_rows():
 def test_gpu_fov_control_matches_oracle(mpclib, n, seed, scale):
     import torch
     if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+        pytest.fail("GPU test needs a visible MI355X")
     cfg, states, desired, rp, nb_xy = _case(n, seed, scale)
     dev = torch.device("cuda", 0)
     t = lambda v, dt=torch.float64: torch.tensor(v, dtype=dt, device=dev)  # noqa: E731
@@ -119,7 +119,7 @@ def test_oracle_slack_mode_relaxes_the_fov_rows():
 def test_gpu_fov_control_slack_matches_oracle(mpclib, n, seed, scale, decay):
     import torch
     if not torch.cuda.is_available():
-        pytest.skip("no GPU")
+        pytest.fail("GPU test needs a visible MI355X")
     cfg, states, desired, rp, nb_xy = _case(n, seed, scale)
     scfg = _slack_cfg(decay)
     cov = _nb_covs(max(len(nb_xy), 1), seed)

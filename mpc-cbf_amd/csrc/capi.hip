@@ -1,6 +1,7 @@
-// capi.hip — the C ABI of include/mpccbf.h: context lifetime, operator upload, launches.
-// No exception crosses this boundary (the reference's std::invalid_argument / runtime_error
-// become MPCCBF_ERR_INVALID_ARGUMENT plus a thread-local message).
+// capi.hip — the C ABI of include/mpccbf.h: context lifetime, operator upload, launches (the entry
+// points that hold no context: capi_control.hip). No exception crosses this boundary (the
+// reference's std::invalid_argument / runtime_error become MPCCBF_ERR_INVALID_ARGUMENT plus a
+// thread-local message).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -16,15 +17,15 @@
 #include <vector>
 
 #include "../../include/mpccbf.h"
-#include "host/errors.hpp"
+#include "host/defer_queues.hpp"
+#include "host/grid_rotation.hpp"
+#include "host/hip_host.hpp"
 #include "host/operators.hpp"
 #include "host/pack_operators.hpp"
 #include "kernels/impc.hpp"
 #include "kernels/cap_audit.hpp"
-#include "kernels/cbf_control.hpp"
 #include "kernels/conn_rows.hpp"
 #include "kernels/launch_plan.hpp"
-#include "kernels/pf_fov.hpp"
 
 namespace mpccbf {
 
@@ -35,38 +36,42 @@ int set_error(int code, const std::string& msg) {
     return code;
 }
 
-static int fail(int code, const std::string& msg) { return set_error(code, msg); }
+// Grid mode's three neighbour tables (GridArgs) in one buffer grown on demand, with the rotation
+// that says which of them a step uses and what a later call may continue (grid_rotation.hpp). The
+// device calls are here; every decision, and the only writes of the continuation record, are rot's.
+struct GridTables {
+    DevBuf buf;
+    GridRotation rot;
+    uint32_t *cnt[3] = {}, *slots[3] = {};
+    double* sst[3] = {};
 
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return fail(MPCCBF_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
+    // the tables of a state table of num_states rows
+    int carve(int num_states) {
+        const size_t tb = grid_table_bytes(num_states);
+        rot.reallocates(3 * tb, buf.bytes);
+        HIP_TRY(buf.reserve(3 * tb));
+        for (int t = 0; t < 3; t++)
+            grid_table_carve(buf.as<char>() + t * tb, num_states, &cnt[t], &slots[t], &sst[t]);
+        return MPCCBF_OK;
+    }
+    // table 0 from these states; zero_fill: table 1 zeroed for the inserts of the step that reads it
+    int rebuild(const double* states, int num_states, double radius, bool zero_fill, hipStream_t stream) {
+        const size_t cb = (size_t)grid_table_size(num_states) * 4;
+        HIP_TRY(hipMemsetAsync(cnt[0], 0, cb, stream));
+        if (zero_fill) HIP_TRY(hipMemsetAsync(cnt[1], 0, cb, stream));
+        HIP_TRY(launch_grid_insert(states, num_states, 0, 0, radius, cnt[0], slots[0], sst[0], stream));
+        return MPCCBF_OK;
+    }
+};
 
-// A device allocation that grows on demand and is freed with its owner. After a failed growth it
-// is empty (bytes == 0), so the next call allocates again.
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    // at least `need` bytes (a buffer that has to grow is reallocated: its contents are gone)
-    hipError_t reserve(size_t need) {
-        if (need <= bytes) return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc(&p, need);
-        if (e == hipSuccess) bytes = need; else p = nullptr;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
+// What the last IMPC launch was, for the calls that report it (mpccbf_kernel_name: the name is
+// share-adaptive in the agents, and the default variant's dense layout depends on where the
+// neighbour lists come from; mpccbf_launch_form)
+struct LastLaunch {
+    int n = 0;
+    bool csr = false;
+    int knn = 0;
+    LaunchForm form = FORM_GENERIC;
 };
 
 }  // namespace mpccbf
@@ -80,19 +85,12 @@ struct mpccbf_ctx {
     int device = 0;
     mpccbf::DevBuf dbuf;          // the packed operators (pack_operators)
     mpccbf::DevBuf scratch;       // mpccbf_build_neighbors
-    mpccbf::DevBuf grid_scratch;  // three neighbour tables (see GridArgs)
-    // fallback queues [count, -, agents...], two (alternating by enqueue parity: the main launch
-    // zeroes the other one's header), zero-initialised
+    mpccbf::GridTables grid;      // grid mode's neighbour tables and their rotation
+    // the two deferral queues (defer_queues.hpp: offsets into defer)
     mpccbf::DevBuf defer;
-    int defer_cap = 0;
-    int defer_parity = 0;
+    mpccbf::DeferQueues queues;
     int variant = 0;
-    int last_n = 0;  // agents of the last IMPC launch (the kernel name depends on it: share-adaptive)
-    // its neighbour lists (the default variant's dense layout depends on them: caller lists, or the
-    // grid's knn_k nearest)
-    bool last_csr = false;
-    int last_knn = 0;
-    mpccbf::LaunchForm last_form = mpccbf::FORM_GENERIC;  // its launch form (mpccbf_launch_form)
+    mpccbf::LastLaunch last;
     // active-set store (mpccbf_set_active_store): the caller's device buffer of store_rows records,
     // or nullptr; store_min_steps as the kernels take it (>= 1, or < 0: export only)
     int32_t* store = nullptr;
@@ -102,8 +100,6 @@ struct mpccbf_ctx {
     // the scratch its iteration-0 launch writes (x0: agents x n doubles, then their statuses)
     int32_t o_EB2 = 0;
     mpccbf::DevBuf audit_scratch;
-    // grid mode: where the previous mpccbf_run_steps call left the table rotation (ABI 12,
-    // mpccbf_run::continue_tables): its final state table, shape, query and the next step's table
     // connectivity rows (mpccbf_set_connectivity): the teams (host copy), the caller's outputs, and
     // the device tables the spectrum launch fills per step and the IMPC launch reads (ConnArgs;
     // allocated at the first solve, rows: the state rows they cover)
@@ -117,12 +113,6 @@ struct mpccbf_ctx {
         mpccbf::DevBuf d_team_ptr, d_team_mode, d_row_team;  // int32
         mpccbf::DevBuf d_team_l2, d_fiedler;                 // double
     } conn;
-    struct {
-        bool valid = false;
-        const double* states = nullptr;
-        int ns = 0, first = 0, count = 0, k = 0, next = 0;
-        double radius = 0.0;
-    } gcont;
 };
 
 using namespace mpccbf;
@@ -134,17 +124,6 @@ static LaunchPlan ctx_plan(const mpccbf_ctx* c, int n, bool csr, int knn_k, bool
 
 // Warm-start threshold when mpccbf_set_active_store is given min_steps = 0
 constexpr int STORE_MIN_STEPS_DEFAULT = 3;
-
-// The three neighbour tables of grid mode in ctx scratch (grown on demand).
-static int grid_tables(mpccbf_ctx* c, int num_states, uint32_t* (&cnt)[3], uint32_t* (&slots)[3],
-                       double* (&sst)[3]) {
-    const size_t tb = grid_table_bytes(num_states);
-    if (3 * tb > c->grid_scratch.bytes) c->gcont.valid = false;  // (the tables a continuation would read go)
-    HIP_TRY(c->grid_scratch.reserve(3 * tb));
-    for (int t = 0; t < 3; t++)
-        grid_table_carve(c->grid_scratch.as<char>() + t * tb, num_states, &cnt[t], &slots[t], &sst[t]);
-    return MPCCBF_OK;
-}
 
 static void conn_free(mpccbf_ctx* c) {
     auto& k = c->conn;
@@ -177,21 +156,16 @@ static int conn_tables(mpccbf_ctx* c, int num_states) {
     return MPCCBF_OK;
 }
 
-// One IMPC step for a batch, enqueued on `stream`; ev0 / ev1 (optional) are recorded around the
-// IMPC kernel alone. Grid mode: gstep < 0 builds table 0 from b->states first (memset + insert
-// kernel); gstep >= 0 (mpccbf_run_steps) reads table gstep % 3, which the previous step filled,
-// has the kernel insert its next states into table (gstep + 1) % 3 and zero table (gstep + 2) % 3.
-// ops / store: the context's (c->dev, c->store), or what the cap audit puts in their place.
-int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                 const DevOps& ops, int32_t* store, int gstep = -1, unsigned long long* kclock = nullptr) {
-    if (!c || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    // any step outside a grid-mode mpccbf_run_steps rotation (mpccbf_impc_solve, the CSR steps of
-    // mpccbf_run_steps) may write the state table a continuation would read: it must rebuild
-    if (gstep < 0) c->gcont.valid = false;
+// ---- the steps of impc_enqueue, in its order ---------------------------------------------------
+
+static int check_agent_range(const mpccbf_batch* b) {
     if (b->num_agents < 0 || b->agent_first < 0 || b->agent_first + b->num_agents > b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent range outside states");
-    if (b->num_agents == 0) return MPCCBF_OK;
-    const bool grid = b->nb_row_ptr == nullptr;
+    return MPCCBF_OK;
+}
+
+// a batch of at least one agent
+static int check_batch(const mpccbf_ctx* c, const mpccbf_batch* b, bool grid, const int32_t* store) {
     if (!b->states || (!grid && !b->nb_col && b->num_states > 1))
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "states / neighbour CSR missing");
     if (grid && (b->knn_k < 1 || !(b->knn_radius > 0)))
@@ -206,72 +180,73 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     if (store && c->store_rows < b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows (" + std::to_string(c->store_rows) +
                                                      ") < num_states (" + std::to_string(b->num_states) + ")");
-    const bool conn = c->conn.on;
-    if (conn && c->conn.team_ptr.back() > b->num_states)
+    if (c->conn.on && c->conn.team_ptr.back() > b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "connectivity: team_ptr ends at row " +
                                                      std::to_string(c->conn.team_ptr.back()) + " > num_states (" +
                                                      std::to_string(b->num_states) + ")");
-    ImpcArgs a;
-    std::memset(&a, 0, sizeof(a));
-    HIP_TRY(hipSetDevice(c->device));
-    ConnArgs cn;
-    std::memset(&cn, 0, sizeof(cn));
-    if (conn) {
-        // this step's spectra, ahead of the IMPC launch on the same stream, from the table it reads
-        const int rc = conn_tables(c, b->num_states);
-        if (rc != MPCCBF_OK) return rc;
-        const auto& k = c->conn;
-        SpectrumArgs sp;
-        std::memset(&sp, 0, sizeof(sp));
-        sp.num_teams = (int32_t)k.team_ptr.size() - 1;
-        sp.team_ptr = k.d_team_ptr.as<int32_t>();
-        sp.states = b->states;
-        sp.first = b->agent_first;
-        sp.count = b->num_agents;
-        sp.dmax = k.dmax;
-        sp.l2_switch = k.l2_switch;
-        sp.team_l2 = k.d_team_l2.as<double>();
-        sp.team_mode = k.d_team_mode.as<int32_t>();
-        sp.fiedler = k.d_fiedler.as<double>();
-        sp.out_l2 = k.out_l2;
-        sp.out_fiedler = k.out_fiedler;
-        HIP_TRY(launch_team_spectrum(sp, stream));
-        cn.row_team = k.d_row_team.as<int32_t>();
-        cn.team_ptr = sp.team_ptr;
-        cn.team_mode = sp.team_mode;
-        cn.team_l2 = sp.team_l2;
-        cn.fiedler = sp.fiedler;
-        cn.dmax = k.dmax;
-        cn.l2_min = k.l2_min;
+    return MPCCBF_OK;
+}
+
+// This step's team spectra, ahead of the IMPC launch on the same stream, from the state table it
+// reads; cn: what the IMPC launch takes from them.
+static int enqueue_spectrum(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, ConnArgs& cn) {
+    const int rc = conn_tables(c, b->num_states);
+    if (rc != MPCCBF_OK) return rc;
+    const auto& k = c->conn;
+    SpectrumArgs sp;
+    std::memset(&sp, 0, sizeof(sp));
+    sp.num_teams = (int32_t)k.team_ptr.size() - 1;
+    sp.team_ptr = k.d_team_ptr.as<int32_t>();
+    sp.states = b->states;
+    sp.first = b->agent_first;
+    sp.count = b->num_agents;
+    sp.dmax = k.dmax;
+    sp.l2_switch = k.l2_switch;
+    sp.team_l2 = k.d_team_l2.as<double>();
+    sp.team_mode = k.d_team_mode.as<int32_t>();
+    sp.fiedler = k.d_fiedler.as<double>();
+    sp.out_l2 = k.out_l2;
+    sp.out_fiedler = k.out_fiedler;
+    HIP_TRY(launch_team_spectrum(sp, stream));
+    cn.row_team = k.d_row_team.as<int32_t>();
+    cn.team_ptr = sp.team_ptr;
+    cn.team_mode = sp.team_mode;
+    cn.team_l2 = sp.team_l2;
+    cn.fiedler = sp.fiedler;
+    cn.dmax = k.dmax;
+    cn.l2_min = k.l2_min;
+    return MPCCBF_OK;
+}
+
+// The step's neighbour tables in their roles. A step outside a rotation (roles.fill < 0) has the
+// table it reads built from b->states first (memset + insert kernel) and fills none.
+static int grid_args(mpccbf_ctx* c, const mpccbf_batch* b, const DevOps& ops, const GridRoles& roles,
+                     hipStream_t stream, GridArgs& g) {
+    GridTables& t = c->grid;
+    const int rc = t.carve(b->num_states);
+    if (rc != MPCCBF_OK) return rc;
+    if (roles.fill < 0) {
+        const int rb = t.rebuild(b->states, b->num_states, b->knn_radius, false, stream);
+        if (rb != MPCCBF_OK) return rb;
+    } else {
+        g.ins_cnt = t.cnt[roles.fill];
+        g.ins_slots = t.slots[roles.fill];
+        g.ins_sst = t.sst[roles.fill];
+        g.clr_cnt = t.cnt[roles.zero];
     }
-    if (grid) {
-        uint32_t *cnt[3], *slots[3];
-        double* sst[3];
-        const int rc = grid_tables(c, b->num_states, cnt, slots, sst);
-        if (rc != MPCCBF_OK) return rc;
-        const uint32_t T = grid_table_size(b->num_states);
-        int rd = 0;
-        if (gstep < 0) {  // (table 0 rebuilt here: gcont was cleared above)
-            HIP_TRY(hipMemsetAsync(cnt[0], 0, (size_t)T * 4, stream));
-            HIP_TRY(launch_grid_insert(b->states, b->num_states, 0, 0, b->knn_radius, cnt[0], slots[0], sst[0],
-                                       stream));
-        } else {
-            rd = gstep % 3;
-            a.grid.ins_cnt = cnt[(gstep + 1) % 3];
-            a.grid.ins_slots = slots[(gstep + 1) % 3];
-            a.grid.ins_sst = sst[(gstep + 1) % 3];
-            a.grid.clr_cnt = cnt[(gstep + 2) % 3];
-        }
-        a.grid.cnt = cnt[rd];
-        a.grid.slots = slots[rd];
-        a.grid.sst = sst[rd];
-        a.grid.mask = T - 1;
-        a.grid.inv_cell = grid_inv_cell(b->knn_radius);  // (as launch_grid_insert's)
-        a.grid.radius = b->knn_radius;
-        a.grid.k = b->knn_k;
-        // FoV controller: only agents inside the field of view are observed neighbours
-        a.grid.cone = (ops.cbf_mode == 1 && ops.fov_beta < 2.0 * M_PI - 1e-9) ? 0.5 * ops.fov_beta : 0.0;
-    }
+    g.cnt = t.cnt[roles.read];
+    g.slots = t.slots[roles.read];
+    g.sst = t.sst[roles.read];
+    g.mask = grid_table_size(b->num_states) - 1;
+    g.inv_cell = grid_inv_cell(b->knn_radius);  // (as launch_grid_insert's)
+    g.radius = b->knn_radius;
+    g.k = b->knn_k;
+    // FoV controller: only agents inside the field of view are observed neighbours
+    g.cone = (ops.cbf_mode == 1 && ops.fov_beta < 2.0 * M_PI - 1e-9) ? 0.5 * ops.fov_beta : 0.0;
+    return MPCCBF_OK;
+}
+
+static void batch_args(const mpccbf_batch* b, unsigned long long* kclock, ImpcArgs& a) {
     a.num_states = b->num_states;
     a.states = b->states;
     a.agent_first = b->agent_first;
@@ -297,55 +272,62 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     a.substeps = b->substeps;
     a.nb_out = b->nb_out;
     a.kclock = kclock;
-    // the launch-uniform options, as the arguments just filled hold them (the plan's loop form)
-    LaunchFacts lf{};
-    lf.targets = a.targets != nullptr;
-    lf.traj_t = a.traj_t != nullptr;
-    lf.substeps = a.substeps != nullptr;
-    lf.cov = a.cov != nullptr;
-    lf.nb_out = a.nb_out != nullptr;
-    lf.primal_res = a.primal_res != nullptr;
-    lf.dual_res = a.dual_res != nullptr;
-    lf.cone = a.grid.cone > 0.0;
-    lf.x = a.x != nullptr;
-    lf.status = a.status != nullptr;
-    lf.obj = a.obj != nullptr;
-    lf.iters = a.iters != nullptr;
-    lf.next_states = a.next_states != nullptr;
-    lf.insert = a.grid.ins_cnt != nullptr;
-    const LaunchPlan plan =
-        impc_launch_plan(ops, c->variant, b->num_agents, !grid, b->knn_k, store != nullptr, conn, lf);
+}
+
+// The queue the main launch appends to and the one whose header it zeroes, each with room for
+// every agent of the batch (growth: the whole buffer zeroed on the stream)
+static int defer_args(mpccbf_ctx* c, int num_agents, hipStream_t stream, ImpcArgs& a) {
+    const int rc = c->queues.ensure(num_agents, [&](size_t bytes) -> int {
+        HIP_TRY(c->defer.reserve(bytes));
+        HIP_TRY(hipMemsetAsync(c->defer.p, 0, bytes, stream));
+        return MPCCBF_OK;
+    });
+    if (rc != MPCCBF_OK) return rc;
+    a.defer = c->defer.as<int32_t>() + c->queues.current();
+    a.defer_clear = c->defer.as<int32_t>() + c->queues.other();
+    return MPCCBF_OK;
+}
+
+// One IMPC step for a batch, enqueued on `stream`; ev0 / ev1 (optional) are recorded around the
+// IMPC kernel alone. run_step >= 0: step run_step of the grid-mode mpccbf_run_steps call that
+// started the rotation (GridRotation::step); < 0: a step outside a rotation (foreign_step).
+// ops / store: the context's (c->dev, c->store), or what the cap audit puts in their place.
+int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                 const DevOps& ops, int32_t* store, int run_step = -1, unsigned long long* kclock = nullptr) {
+    if (!c || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    const GridRoles roles = run_step < 0 ? c->grid.rot.foreign_step() : c->grid.rot.step(run_step);
+    // validate
+    int rc = check_agent_range(b);
+    if (rc != MPCCBF_OK || b->num_agents == 0) return rc;
+    const bool grid = b->nb_row_ptr == nullptr, conn = c->conn.on;
+    if ((rc = check_batch(c, b, grid, store)) != MPCCBF_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // spectrum, grid arguments, the batch's fields
+    ImpcArgs a;
+    std::memset(&a, 0, sizeof(a));
+    ConnArgs cn;
+    std::memset(&cn, 0, sizeof(cn));
+    if (conn && (rc = enqueue_spectrum(c, b, stream, cn)) != MPCCBF_OK) return rc;
+    if (grid && (rc = grid_args(c, b, ops, roles, stream, a.grid)) != MPCCBF_OK) return rc;
+    batch_args(b, kclock, a);
+    // facts and plan
+    const LaunchPlan plan = impc_launch_plan(ops, c->variant, b->num_agents, !grid, b->knn_k, store != nullptr, conn,
+                                             launch_facts(a));
     if (b->substeps && !b->traj_t)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "substeps (closed-loop records) needs traj_t");
-    // fallback launch: agents the main launch defers (the lean launch: QPs that need the PDIP or
-    // phase 1; beyond the separable kernel's 16 CBF row slots) are solved by a second launch of
-    // the full separable pipeline (128 slots when the 16 can be exceeded)
-    // (the connectivity launch has no capacity launch behind it: beyond its rows, ERROR)
-    const bool fb = plan.defer;
-    // the store: read and written by the kernels that support it; any other launch leaves its
-    // agents' records zero (no record), so a record never outlives the solve it describes
+    // store reset: the store is read and written by the kernels that support it; any other launch
+    // leaves its agents' records zero (no record), so a record never outlives the solve it describes
     const StoreArgs st{store, c->store_min_steps};
     if (store && !plan.store)
         HIP_TRY(hipMemsetAsync(store + (size_t)b->agent_first * AS_WORDS, 0,
                                (size_t)b->num_agents * AS_WORDS * sizeof(int32_t), stream));
-    c->last_n = b->num_agents;
-    c->last_csr = !grid;
-    c->last_knn = b->knn_k;
-    c->last_form = plan.form;
-    if (fb && c->defer_cap < b->num_agents) {
-        const size_t bytes = 2 * (size_t)(b->num_agents + 2) * sizeof(int32_t);
-        c->defer_cap = 0;
-        HIP_TRY(c->defer.reserve(bytes));
-        HIP_TRY(hipMemsetAsync(c->defer.p, 0, bytes, stream));
-        c->defer_cap = b->num_agents;
-        c->defer_parity = 0;
-    }
-    int32_t* q_this = nullptr;
-    if (fb) {
-        q_this = c->defer.as<int32_t>() + (size_t)c->defer_parity * (c->defer_cap + 2);
-        a.defer_clear = c->defer.as<int32_t>() + (size_t)(c->defer_parity ^ 1) * (c->defer_cap + 2);
-    }
-    a.defer = q_this;
+    c->last = LastLaunch{b->num_agents, !grid, b->knn_k, plan.form};
+    // queues: agents the main launch defers (the lean launch: QPs that need the PDIP or phase 1;
+    // beyond the separable kernel's 16 CBF row slots) are solved by a second launch of the full
+    // separable pipeline (128 slots when the 16 can be exceeded)
+    // (the connectivity launch has no capacity launch behind it: beyond its rows, ERROR)
+    if (plan.defer && (rc = defer_args(c, b->num_agents, stream, a)) != MPCCBF_OK) return rc;
+    // main launch
     if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
     const double* buf = c->dbuf.as<double>();
     // one launcher per translation unit that instantiates IMPC kernels (launch_plan.hpp)
@@ -357,18 +339,18 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         return launch_impc(k, blocks, bs, ops, buf, ia, stream);
     };
     hipError_t e = launch(plan.kernel, plan.block_size, plan.agents_per_block, a);
-    // the queues alternate only once the main launch is enqueued: a launch that failed zeroed no
-    // header, so the next call must append to this step's queue again (zeroed by the launch before)
-    if (e == hipSuccess && fb) c->defer_parity ^= 1;
-    if (e == hipSuccess && fb) {
+    if (plan.defer) c->queues.advance(e == hipSuccess);
+    // capacity launch
+    if (e == hipSuccess && plan.defer) {
         ImpcArgs f = a;
         f.defer = nullptr;
         f.defer_clear = nullptr;
         f.kclock = nullptr;  // (the clock is the main launch's)
-        f.queue = q_this;
+        f.queue = a.defer;
         e = launch(plan.capacity, IMPC_QUEUE_BLOCK, IMPC_QUEUE_AGENTS, f);
         // (a queue the fallback never read is zeroed by the main launch after next)
     }
+    // events
     if (e == hipSuccess && ev1) e = hipEventRecord(ev1, stream);
     if (e == hipErrorInvalidValue)
         return fail(MPCCBF_ERR_CAPACITY, "no kernel instantiation for this reduced dimension / row count");
@@ -461,10 +443,10 @@ int32_t mpccbf_impc_launch_waves(const mpccbf_ctx* c, int32_t num_agents) {
 }
 
 const char* mpccbf_kernel_name(const mpccbf_ctx* c) {
-    return c ? ctx_plan(c, c->last_n, c->last_csr, c->last_knn, c->store != nullptr).name : "";
+    return c ? ctx_plan(c, c->last.n, c->last.csr, c->last.knn, c->store != nullptr).name : "";
 }
 
-const char* mpccbf_launch_form(const mpccbf_ctx* c) { return launch_form_name(c ? c->last_form : FORM_GENERIC); }
+const char* mpccbf_launch_form(const mpccbf_ctx* c) { return launch_form_name(c ? c->last.form : FORM_GENERIC); }
 
 int mpccbf_set_active_store(mpccbf_ctx* c, int32_t* store, int32_t rows, int32_t min_steps) {
     if (rows < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows must be >= 0");
@@ -557,7 +539,8 @@ int mpccbf_cap_audit_run(mpccbf_ctx* c, const mpccbf_batch* b, const mpccbf_cap_
     int32_t* st0 = (int32_t*)(c->audit_scratch.as<char>() + xbytes);
     // iteration 0's solutions: the context's own IMPC launch once more on the same batch with one
     // iteration, every output into scratch, no closed-loop state, no diagnostics, no active store
-    // (grid mode: gstep < 0 rebuilds the table from b->states, so the lists are the solve's)
+    // (grid mode: a step outside a rotation rebuilds the table from b->states, so the lists are the
+    // solve's)
     {
         mpccbf_batch sb = *b;
         sb.x = x0;
@@ -766,7 +749,7 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
         // entry: that write follows this call's step barriers, or the abort below)
         if (!same) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: ranks of the in-process group differ in num_steps");
         if (r->num_steps == 0) {
-            c->gcont.valid = false;  // (as every call that does not end a grid rotation, see below)
+            c->grid.rot.no_rotation();
             if (!lg->barrier()) return fail(MPCCBF_ERR_HIP, "run: a rank of the in-process group aborted");
             guard.g = nullptr;
             return MPCCBF_OK;
@@ -799,36 +782,21 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
     mpccbf_batch sb = *b;
     hipEvent_t* ev = c->events.data();
     if (timing) HIP_TRY(hipEventRecord(ev[0], stream));
-    // grid mode: neighbour table 0 from the initial states, table 1 zeroed for step 0's inserts
-    // (each IMPC launch zeroes the table two steps ahead, see impc_enqueue)
+    // grid mode: the rotation of the previous call continued, or neighbour table 0 from the initial
+    // states and table 1 zeroed for step 0's inserts (each IMPC launch zeroes the table two steps
+    // ahead). Only a grid-mode call that runs at least one step leaves a rotation to continue.
     const bool gtab = b->nb_row_ptr == nullptr && count > 0 && r->num_steps > 0;
-    uint32_t *gcnt[3] = {}, *gslots[3] = {};
-    double* gsst[3] = {};
-    int gbase = 0;  // the first step's table index (gstep = gbase + s)
-    // Only a grid-mode call that ran at least one step leaves a rotation to continue. Every other
-    // call (CSR lists, zero steps, zero agents) clears the record: its steps, or the caller around
-    // a call that ran none, may have rewritten the recorded state table, whose states the
-    // neighbour table holds copies of.
-    if (!gtab) c->gcont.valid = false;
+    GridTables& gt = c->grid;
+    if (!gtab) gt.rot.no_rotation();
     if (gtab) {
         if (b->knn_k < 1 || !(b->knn_radius > 0))
             return fail(MPCCBF_ERR_INVALID_ARGUMENT, "grid neighbours need knn_k >= 1 and knn_radius > 0");
-        const int rc = grid_tables(c, ns, gcnt, gslots, gsst);
+        int rc = gt.carve(ns);
         if (rc != MPCCBF_OK) return rc;
-        const auto& g = c->gcont;
-        const bool cont = r->continue_tables && g.valid && g.states == b->states && g.ns == ns && g.first == first &&
-                          g.count == count && g.k == b->knn_k && g.radius == b->knn_radius;
-        if (cont) {
-            // the previous call's last step filled table g.next with these states and zeroed the
-            // one after it: this call's first step reads the former and fills the latter
-            gbase = g.next;
-        } else {
-            const size_t cb = (size_t)grid_table_size(ns) * 4;
-            HIP_TRY(hipMemsetAsync(gcnt[0], 0, cb, stream));
-            HIP_TRY(hipMemsetAsync(gcnt[1], 0, cb, stream));
-            HIP_TRY(launch_grid_insert(b->states, ns, 0, 0, b->knn_radius, gcnt[0], gslots[0], gsst[0], stream));
-        }
-        c->gcont.valid = false;  // (set again once every step is enqueued)
+        const GridQuery q{b->states, ns, first, count, b->knn_k, b->knn_radius};
+        if (gt.rot.run_started(q, r->continue_tables != 0) < 0 &&
+            (rc = gt.rebuild(b->states, ns, b->knn_radius, true, stream)) != MPCCBF_OK)
+            return rc;
     }
     for (int s = 0; s < r->num_steps; s++) {
         double* cur = tables[s & 1];
@@ -848,7 +816,7 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
         }
         const bool tk = r->solve_ms && (r->solve_stride <= 1 || s % r->solve_stride == 0);
         const int rc = impc_enqueue(c, &sb, stream, tk ? ev[3 * s + 1] : nullptr, tk ? ev[3 * s + 2] : nullptr,
-                                    c->dev, c->store, gtab ? gbase + s : -1,
+                                    c->dev, c->store, gtab ? s : -1,
                                     r->kernel_clock ? (unsigned long long*)r->kernel_clock +
                                                           2 * (size_t)r->kernel_clock_waves * s
                                                     : nullptr);
@@ -874,25 +842,16 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
         // the rows the kernel did not insert (static rows / the other ranks' rows) join the table
         // of the next step
         if (gtab && count < ns) {
-            const int t = (gbase + s + 1) % 3;
-            HIP_TRY(launch_grid_insert(nxt, ns, first, first + count, b->knn_radius, gcnt[t], gslots[t], gsst[t],
-                                       stream));
+            const int t = gt.rot.step(s).fill;
+            HIP_TRY(launch_grid_insert(nxt, ns, first, first + count, b->knn_radius, gt.cnt[t], gt.slots[t],
+                                       gt.sst[t], stream));
         }
         if (r->step_ms || (timing && s == r->num_steps - 1)) HIP_TRY(hipEventRecord(ev[3 * s + 3], stream));
     }
     guard.g = nullptr;  // every barrier of the call passed: the peers no longer wait on this rank
     r->final_table = r->num_steps & 1;
-    if (gtab) {  // where a continuing call picks the rotation up (mpccbf_run::continue_tables)
-        auto& g = c->gcont;
-        g.valid = true;
-        g.states = tables[r->num_steps & 1];
-        g.ns = ns;
-        g.first = first;
-        g.count = count;
-        g.k = b->knn_k;
-        g.radius = b->knn_radius;
-        g.next = (gbase + r->num_steps) % 3;
-    }
+    // where a continuing call picks the rotation up (mpccbf_run::continue_tables)
+    if (gtab) gt.rot.run_finished(tables[r->num_steps & 1], r->num_steps);
     if (timing && r->num_steps > 0) {
         HIP_TRY(hipEventSynchronize(ev[3 * (r->num_steps - 1) + 3]));
         for (int s = 0; s < r->num_steps; s++) {
@@ -912,196 +871,6 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
         }
     }
     return MPCCBF_OK;
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int mpccbf_connectivity_control_solve(const mpccbf_connectivity_control_params* p,
-                                      const mpccbf_connectivity_control_batch* b, int32_t device,
-                                      void* stream) {
-    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    if (!(p->d_min > 0.0) || !(p->d_max > 0.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "d_min and d_max must be positive");
-    for (int d = 0; d < 3; d++)
-        if (!(p->v_min[d] <= p->v_max[d])) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "v_min must not exceed v_max");
-    if (p->slack_mode && !(p->slack_cost > 0.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack cost must be positive when slack_mode is enabled");
-    if (p->slack_mode && !(p->slack_decay_rate > 0.0 && p->slack_decay_rate <= 1.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack decay rate must be in (0,1] when slack_mode is enabled");
-    if (b->num_teams < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_teams < 0");
-    if (b->num_teams == 0) return MPCCBF_OK;
-    if (!b->team_ptr || !b->states || !b->desired_u || !b->u)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "team_ptr, states, desired_u and u are required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
-    HIP_TRY(hipSetDevice(device));
-    ConnControlArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.num_teams = b->num_teams;
-    a.team_ptr = b->team_ptr;
-    a.states = b->states;
-    a.desired_u = b->desired_u;
-    a.u = b->u;
-    a.status = b->status;
-    a.obj = b->obj;
-    a.iters = b->iters;
-    a.lambda2 = b->lambda2;
-    a.dmin = p->d_min;
-    a.dmax = p->d_max;
-    for (int d = 0; d < 3; d++) {
-        a.vmin[d] = p->v_min[d];
-        a.vmax[d] = p->v_max[d];
-    }
-    a.maxit = p->max_pdip_iters > 0 ? p->max_pdip_iters : 60;
-    a.tol = p->tolerance > 0.0 ? p->tolerance : 1e-9;
-    a.feas_tol = 1e-6;
-    a.slack_mode = p->slack_mode ? 1 : 0;
-    a.slack_cost = p->slack_cost;
-    a.slack_decay = p->slack_decay_rate;
-    HIP_TRY(launch_connectivity_control(a, (hipStream_t)stream));
-    return MPCCBF_OK;
-}
-
-int mpccbf_fov_rows_eval(int32_t count, const double* ego, const double* nb_xy, double fov, double Ds,
-                         double Rs, const double* bbox, double* voronoi, double* fov_rows, void* stream) {
-    if (count < 0 || (count > 0 && (!ego || !nb_xy))) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "bad arguments");
-    if (count == 0) return MPCCBF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
-    const double bbx = bbox ? bbox[0] : 0.0, bby = bbox ? bbox[1] : 0.0;
-    HIP_TRY(launch_fov_rows_eval(count, ego, nb_xy, fov, Ds, Rs, bbx, bby, voronoi, fov_rows, (hipStream_t)stream));
-    return MPCCBF_OK;
-}
-
-int mpccbf_fov_control_solve(const mpccbf_fov_control_params* p, const mpccbf_fov_control_batch* b,
-                             int32_t device, void* stream) {
-    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    if (p->slack_mode && !(p->slack_cost > 0.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack cost must be positive when slack_mode is enabled");
-    if (p->slack_mode && !(p->slack_decay_rate > 0.0 && p->slack_decay_rate <= 1.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack decay rate must be in (0,1] when slack_mode is enabled");
-    if (!(p->fov > 0.0) || !(p->Rs > 0.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "fov and Rs must be positive");
-    for (int d = 0; d < 3; d++)
-        if (!(p->u_min[d] <= p->u_max[d]) || !(p->v_min[d] <= p->v_max[d]))
-            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "bounds: min must not exceed max");
-    if (b->num_agents < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_agents < 0");
-    if (b->num_agents == 0) return MPCCBF_OK;
-    if (!b->states || !b->desired_u || !b->nb_row_ptr || !b->u)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "states, desired_u, nb_row_ptr and u are required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
-    HIP_TRY(hipSetDevice(device));
-    FovControlArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.num_agents = b->num_agents;
-    a.states = b->states;
-    a.desired_u = b->desired_u;
-    a.nb_row_ptr = b->nb_row_ptr;
-    a.nb_xy = b->nb_xy;
-    a.u = b->u;
-    a.status = b->status;
-    a.obj = b->obj;
-    a.iters = b->iters;
-    a.fov = p->fov;
-    a.Ds = p->Ds;
-    a.Rs = p->Rs;
-    for (int d = 0; d < 3; d++) {
-        a.vmin[d] = p->v_min[d];
-        a.vmax[d] = p->v_max[d];
-        a.umin[d] = p->u_min[d];
-        a.umax[d] = p->u_max[d];
-    }
-    a.maxit = p->max_pdip_iters > 0 ? p->max_pdip_iters : 60;
-    a.tol = p->tolerance > 0.0 ? p->tolerance : 1e-9;
-    a.feas_tol = 1e-6;  // CPLEX's default feasibility tolerance
-    for (int i = 0; i < 9; i++) {
-        a.P[i] = (i % 4 == 0) ? 2.0 : 0.0;  // ||u - u_des||^2 = 1/2 u^T (2 I) u - 2 u_des^T u + c
-        a.LP[i] = (i % 4 == 0) ? std::sqrt(2.0) : 0.0;
-    }
-    a.slack_mode = p->slack_mode ? 1 : 0;
-    a.slack_cost = p->slack_cost;
-    a.slack_decay = p->slack_decay_rate;
-    a.nb_cov = b->nb_cov;
-    HIP_TRY(launch_fov_control(a, (hipStream_t)stream));
-    return MPCCBF_OK;
-}
-
-// mpccbf_pf_init / mpccbf_pf_step: every argument check runs on the host before any device call
-static int pf_call(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream,
-                   bool init) {
-    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    if (p->num_particles < PF_MIN_PARTICLES || p->num_particles > PF_MAX_PARTICLES)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_particles must be in 2 .. 1024");
-    auto pos_def = [](const double* c) {
-        return c[0] > 0.0 && c[0] * c[2] - c[1] * c[1] > 0.0 && std::isfinite(c[0]) && std::isfinite(c[1]) &&
-               std::isfinite(c[2]);
-    };
-    if (!pos_def(p->init_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "init_cov must be positive definite");
-    if (!pos_def(p->meas_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "meas_cov must be positive definite");
-    if (!(p->weight_reduction > 0.0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "weight_reduction must be positive");
-    if (b->num_states < 0 || b->num_agents < 0 || b->num_pairs < 0 || b->agent_first < 0)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "negative count");
-    if ((int64_t)b->agent_first + b->num_agents > b->num_states)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent_first + num_agents exceeds num_states");
-    if (b->num_pairs == 0 || b->num_agents == 0) return MPCCBF_OK;
-    if (!b->states || !b->nb_row_ptr || !b->nb_col || !b->particles || !b->weights || !b->est_xy || !b->est_cov)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT,
-                    "states, nb_row_ptr, nb_col, particles, weights, est_xy and est_cov are required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
-    HIP_TRY(hipSetDevice(device));
-    PfArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.num_particles = p->num_particles;
-    a.num_states = b->num_states;
-    a.states = b->states;
-    a.agent_first = b->agent_first;
-    a.num_agents = b->num_agents;
-    a.nb_row_ptr = b->nb_row_ptr;
-    a.nb_col = b->nb_col;
-    a.num_pairs = b->num_pairs;
-    a.input = b->input;
-    a.init_xy = b->init_xy;
-    a.particles = b->particles;
-    a.weights = b->weights;
-    a.est_xy = b->est_xy;
-    a.est_cov = b->est_cov;
-    a.flags = b->flags;
-    a.ancestors = b->ancestors;
-    a.step_index = b->step_index;
-    a.seed = p->seed;
-    for (int i = 0; i < 3; i++) a.init_cov[i] = p->init_cov[i];
-    // Eigen::LLT of init_cov (particle_filter.cpp:38-39)
-    a.init_chol[0] = std::sqrt(p->init_cov[0]);
-    a.init_chol[1] = p->init_cov[1] / a.init_chol[0];
-    a.init_chol[2] = std::sqrt(p->init_cov[2] - a.init_chol[1] * a.init_chol[1]);
-    for (int i = 0; i < 4; i++) a.process[i] = p->process[i];
-    // cov.inverse() of the measurement covariance (particle_filter.cpp:96)
-    const double det = p->meas_cov[0] * p->meas_cov[2] - p->meas_cov[1] * p->meas_cov[1];
-    a.meas_inv[0] = p->meas_cov[2] / det;
-    a.meas_inv[1] = -p->meas_cov[1] / det;
-    a.meas_inv[2] = p->meas_cov[0] / det;
-    a.dt = p->dt;
-    a.fov = p->fov;
-    a.Rs = p->Rs;
-    a.weight_reduction = p->weight_reduction;
-    HIP_TRY(init ? launch_pf_init(a, (hipStream_t)stream) : launch_pf_step(a, (hipStream_t)stream));
-    return MPCCBF_OK;
-}
-
-int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
-    return pf_call(p, b, device, stream, true);
-}
-
-int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
-    return pf_call(p, b, device, stream, false);
 }
 
 }  // extern "C"

@@ -1,0 +1,207 @@
+// capi_control.hip — the C ABI's entry points that hold no context: the CBF-only controllers
+// (mpccbf_connectivity_control_solve, mpccbf_fov_rows_eval, mpccbf_fov_control_solve) and the FoV
+// particle filter (mpccbf_pf_init, mpccbf_pf_step). Each checks its arguments on the host, fills the
+// kernel's argument struct and enqueues one launch.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/mpccbf.h"
+#include "host/hip_host.hpp"
+#include "kernels/cbf_control.hpp"
+#include "kernels/launch_plan.hpp"
+#include "kernels/pf_fov.hpp"
+
+using namespace mpccbf;
+
+extern "C" {
+
+int mpccbf_connectivity_control_solve(const mpccbf_connectivity_control_params* p,
+                                      const mpccbf_connectivity_control_batch* b, int32_t device,
+                                      void* stream) {
+    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    if (!(p->d_min > 0.0) || !(p->d_max > 0.0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "d_min and d_max must be positive");
+    for (int d = 0; d < 3; d++)
+        if (!(p->v_min[d] <= p->v_max[d])) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "v_min must not exceed v_max");
+    if (p->slack_mode && !(p->slack_cost > 0.0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack cost must be positive when slack_mode is enabled");
+    if (p->slack_mode && !(p->slack_decay_rate > 0.0 && p->slack_decay_rate <= 1.0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack decay rate must be in (0,1] when slack_mode is enabled");
+    if (b->num_teams < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_teams < 0");
+    if (b->num_teams == 0) return MPCCBF_OK;
+    if (!b->team_ptr || !b->states || !b->desired_u || !b->u)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "team_ptr, states, desired_u and u are required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    ConnControlArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.num_teams = b->num_teams;
+    a.team_ptr = b->team_ptr;
+    a.states = b->states;
+    a.desired_u = b->desired_u;
+    a.u = b->u;
+    a.status = b->status;
+    a.obj = b->obj;
+    a.iters = b->iters;
+    a.lambda2 = b->lambda2;
+    a.dmin = p->d_min;
+    a.dmax = p->d_max;
+    for (int d = 0; d < 3; d++) {
+        a.vmin[d] = p->v_min[d];
+        a.vmax[d] = p->v_max[d];
+    }
+    a.maxit = p->max_pdip_iters > 0 ? p->max_pdip_iters : 60;
+    a.tol = p->tolerance > 0.0 ? p->tolerance : 1e-9;
+    a.feas_tol = 1e-6;
+    a.slack_mode = p->slack_mode ? 1 : 0;
+    a.slack_cost = p->slack_cost;
+    a.slack_decay = p->slack_decay_rate;
+    HIP_TRY(launch_connectivity_control(a, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+int mpccbf_fov_rows_eval(int32_t count, const double* ego, const double* nb_xy, double fov, double Ds,
+                         double Rs, const double* bbox, double* voronoi, double* fov_rows, void* stream) {
+    if (count < 0 || (count > 0 && (!ego || !nb_xy))) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (count == 0) return MPCCBF_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    const double bbx = bbox ? bbox[0] : 0.0, bby = bbox ? bbox[1] : 0.0;
+    HIP_TRY(launch_fov_rows_eval(count, ego, nb_xy, fov, Ds, Rs, bbx, bby, voronoi, fov_rows, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+int mpccbf_fov_control_solve(const mpccbf_fov_control_params* p, const mpccbf_fov_control_batch* b,
+                             int32_t device, void* stream) {
+    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    if (p->slack_mode && !(p->slack_cost > 0.0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack cost must be positive when slack_mode is enabled");
+    if (p->slack_mode && !(p->slack_decay_rate > 0.0 && p->slack_decay_rate <= 1.0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack decay rate must be in (0,1] when slack_mode is enabled");
+    if (!(p->fov > 0.0) || !(p->Rs > 0.0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "fov and Rs must be positive");
+    for (int d = 0; d < 3; d++)
+        if (!(p->u_min[d] <= p->u_max[d]) || !(p->v_min[d] <= p->v_max[d]))
+            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "bounds: min must not exceed max");
+    if (b->num_agents < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_agents < 0");
+    if (b->num_agents == 0) return MPCCBF_OK;
+    if (!b->states || !b->desired_u || !b->nb_row_ptr || !b->u)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "states, desired_u, nb_row_ptr and u are required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    FovControlArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.num_agents = b->num_agents;
+    a.states = b->states;
+    a.desired_u = b->desired_u;
+    a.nb_row_ptr = b->nb_row_ptr;
+    a.nb_xy = b->nb_xy;
+    a.u = b->u;
+    a.status = b->status;
+    a.obj = b->obj;
+    a.iters = b->iters;
+    a.fov = p->fov;
+    a.Ds = p->Ds;
+    a.Rs = p->Rs;
+    for (int d = 0; d < 3; d++) {
+        a.vmin[d] = p->v_min[d];
+        a.vmax[d] = p->v_max[d];
+        a.umin[d] = p->u_min[d];
+        a.umax[d] = p->u_max[d];
+    }
+    a.maxit = p->max_pdip_iters > 0 ? p->max_pdip_iters : 60;
+    a.tol = p->tolerance > 0.0 ? p->tolerance : 1e-9;
+    a.feas_tol = 1e-6;  // CPLEX's default feasibility tolerance
+    for (int i = 0; i < 9; i++) {
+        a.P[i] = (i % 4 == 0) ? 2.0 : 0.0;  // ||u - u_des||^2 = 1/2 u^T (2 I) u - 2 u_des^T u + c
+        a.LP[i] = (i % 4 == 0) ? std::sqrt(2.0) : 0.0;
+    }
+    a.slack_mode = p->slack_mode ? 1 : 0;
+    a.slack_cost = p->slack_cost;
+    a.slack_decay = p->slack_decay_rate;
+    a.nb_cov = b->nb_cov;
+    HIP_TRY(launch_fov_control(a, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+// mpccbf_pf_init / mpccbf_pf_step: every argument check runs on the host before any device call
+static int pf_call(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream,
+                   bool init) {
+    if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    if (p->num_particles < PF_MIN_PARTICLES || p->num_particles > PF_MAX_PARTICLES)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_particles must be in 2 .. 1024");
+    auto pos_def = [](const double* c) {
+        return c[0] > 0.0 && c[0] * c[2] - c[1] * c[1] > 0.0 && std::isfinite(c[0]) && std::isfinite(c[1]) &&
+               std::isfinite(c[2]);
+    };
+    if (!pos_def(p->init_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "init_cov must be positive definite");
+    if (!pos_def(p->meas_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "meas_cov must be positive definite");
+    if (!(p->weight_reduction > 0.0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "weight_reduction must be positive");
+    if (b->num_states < 0 || b->num_agents < 0 || b->num_pairs < 0 || b->agent_first < 0)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "negative count");
+    if ((int64_t)b->agent_first + b->num_agents > b->num_states)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent_first + num_agents exceeds num_states");
+    if (b->num_pairs == 0 || b->num_agents == 0) return MPCCBF_OK;
+    if (!b->states || !b->nb_row_ptr || !b->nb_col || !b->particles || !b->weights || !b->est_xy || !b->est_cov)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT,
+                    "states, nb_row_ptr, nb_col, particles, weights, est_xy and est_cov are required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    PfArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.num_particles = p->num_particles;
+    a.num_states = b->num_states;
+    a.states = b->states;
+    a.agent_first = b->agent_first;
+    a.num_agents = b->num_agents;
+    a.nb_row_ptr = b->nb_row_ptr;
+    a.nb_col = b->nb_col;
+    a.num_pairs = b->num_pairs;
+    a.input = b->input;
+    a.init_xy = b->init_xy;
+    a.particles = b->particles;
+    a.weights = b->weights;
+    a.est_xy = b->est_xy;
+    a.est_cov = b->est_cov;
+    a.flags = b->flags;
+    a.ancestors = b->ancestors;
+    a.step_index = b->step_index;
+    a.seed = p->seed;
+    for (int i = 0; i < 3; i++) a.init_cov[i] = p->init_cov[i];
+    // Eigen::LLT of init_cov (particle_filter.cpp:38-39)
+    a.init_chol[0] = std::sqrt(p->init_cov[0]);
+    a.init_chol[1] = p->init_cov[1] / a.init_chol[0];
+    a.init_chol[2] = std::sqrt(p->init_cov[2] - a.init_chol[1] * a.init_chol[1]);
+    for (int i = 0; i < 4; i++) a.process[i] = p->process[i];
+    // cov.inverse() of the measurement covariance (particle_filter.cpp:96)
+    const double det = p->meas_cov[0] * p->meas_cov[2] - p->meas_cov[1] * p->meas_cov[1];
+    a.meas_inv[0] = p->meas_cov[2] / det;
+    a.meas_inv[1] = -p->meas_cov[1] / det;
+    a.meas_inv[2] = p->meas_cov[0] / det;
+    a.dt = p->dt;
+    a.fov = p->fov;
+    a.Rs = p->Rs;
+    a.weight_reduction = p->weight_reduction;
+    HIP_TRY(init ? launch_pf_init(a, (hipStream_t)stream) : launch_pf_step(a, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
+    return pf_call(p, b, device, stream, true);
+}
+
+int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
+    return pf_call(p, b, device, stream, false);
+}
+
+}  // extern "C"

@@ -51,6 +51,26 @@ struct LaunchFacts {
     bool insert;       // the launch fills the next step's neighbour table (GridArgs::ins_cnt)
 };
 
+// The facts of these arguments, as a launch with them holds them
+inline LaunchFacts launch_facts(const ImpcArgs& a) {
+    LaunchFacts f{};
+    f.targets = a.targets != nullptr;
+    f.traj_t = a.traj_t != nullptr;
+    f.substeps = a.substeps != nullptr;
+    f.cov = a.cov != nullptr;
+    f.nb_out = a.nb_out != nullptr;
+    f.primal_res = a.primal_res != nullptr;
+    f.dual_res = a.dual_res != nullptr;
+    f.cone = a.grid.cone > 0.0;
+    f.x = a.x != nullptr;
+    f.status = a.status != nullptr;
+    f.obj = a.obj != nullptr;
+    f.iters = a.iters != nullptr;
+    f.next_states = a.next_states != nullptr;
+    f.insert = a.grid.ins_cnt != nullptr;
+    return f;
+}
+
 struct LaunchPlan {
     ImpcKernel kernel;    // the main launch
     const char* name;     // its instantiation ("": none fits; the FoV and connectivity names are

@@ -56,6 +56,27 @@ constexpr int VARIANT_SEP16 = 4, VARIANT_WIDE = 5;
 
 const char* launch_form_name(LaunchForm f) { return f == FORM_LOOP ? "loop" : "generic"; }
 
+// The facts a caller gives as a bit set of MPCCBF_FACT_* (mpccbf_host_launch_form)
+static LaunchFacts launch_facts_of_bits(uint32_t bits) {
+    auto on = [&](int bit) { return ((bits >> bit) & 1u) != 0; };
+    LaunchFacts f{};
+    f.targets = on(MPCCBF_FACT_TARGETS);
+    f.traj_t = on(MPCCBF_FACT_TRAJ_T);
+    f.substeps = on(MPCCBF_FACT_SUBSTEPS);
+    f.cov = on(MPCCBF_FACT_COV);
+    f.nb_out = on(MPCCBF_FACT_NB_OUT);
+    f.primal_res = on(MPCCBF_FACT_PRIMAL_RES);
+    f.dual_res = on(MPCCBF_FACT_DUAL_RES);
+    f.cone = on(MPCCBF_FACT_CONE);
+    f.x = on(MPCCBF_FACT_X);
+    f.status = on(MPCCBF_FACT_STATUS);
+    f.obj = on(MPCCBF_FACT_OBJ);
+    f.iters = on(MPCCBF_FACT_ITERS);
+    f.next_states = on(MPCCBF_FACT_NEXT_STATES);
+    f.insert = on(MPCCBF_FACT_INSERT);
+    return f;
+}
+
 LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int knn_k, bool store, bool conn,
                             const LaunchFacts& f) {
     // the separable layout with one row slot per lane and channel (up to 16 box rows per channel)
@@ -380,24 +401,8 @@ extern "C" int mpccbf_host_launch_form(const mpccbf_params* p, const mpccbf_opti
     try {
         PackedOps po = pack_operators(build_operators(*p, o.keep_redundant != 0), *p, o);
         po.dev.wide_max = wide_max;
-        auto on = [&](int bit) { return ((facts >> bit) & 1u) != 0; };
-        LaunchFacts f{};
-        f.targets = on(MPCCBF_FACT_TARGETS);
-        f.traj_t = on(MPCCBF_FACT_TRAJ_T);
-        f.substeps = on(MPCCBF_FACT_SUBSTEPS);
-        f.cov = on(MPCCBF_FACT_COV);
-        f.nb_out = on(MPCCBF_FACT_NB_OUT);
-        f.primal_res = on(MPCCBF_FACT_PRIMAL_RES);
-        f.dual_res = on(MPCCBF_FACT_DUAL_RES);
-        f.cone = on(MPCCBF_FACT_CONE);
-        f.x = on(MPCCBF_FACT_X);
-        f.status = on(MPCCBF_FACT_STATUS);
-        f.obj = on(MPCCBF_FACT_OBJ);
-        f.iters = on(MPCCBF_FACT_ITERS);
-        f.next_states = on(MPCCBF_FACT_NEXT_STATES);
-        f.insert = on(MPCCBF_FACT_INSERT);
-        const LaunchPlan pl =
-            impc_launch_plan(po.dev, variant, num_agents, csr != 0, knn_k, store != 0, connectivity != 0, f);
+        const LaunchPlan pl = impc_launch_plan(po.dev, variant, num_agents, csr != 0, knn_k, store != 0,
+                                               connectivity != 0, launch_facts_of_bits(facts));
         if (kernel_id) *kernel_id = pl.kernel;
         if (kernel_name) *kernel_name = pl.name;
         if (form) *form = launch_form_name(pl.form);

@@ -39,6 +39,7 @@
 #include "../../include/mpccbf.h"
 #include "host/dense_pack.hpp"
 #include "host/dense_qp.hpp"
+#include "host/dense_route.hpp"
 #include "host/errors.hpp"
 #include "kernels/group.hpp"
 #include "kernels/das_wave.hpp"
@@ -46,17 +47,8 @@
 
 namespace mpccbf {
 
-constexpr int DENSE_NZ = 8;        // reduced dimension (padded)
-constexpr int DENSE_ROWS = 256;    // reduced inequality rows: 64 lanes x 4 slots
-constexpr int DENSE_NMAX = 64;     // variables per QP (lane = variable)
-constexpr int DENSE_EMAX = 64;     // equalities per QP (lane = equality)
-constexpr int DQ_R = DENSE_ROWS / 64;
-constexpr int DQ_HDR = 2 * DENSE_NZ * DENSE_NZ + DENSE_NZ + 2;  // P, LP, q, reg, pad
-constexpr int DQ_ROW = DENSE_NZ + 2;                            // g, lo, hi
-constexpr double kInf = 1e300;     // |bound| >= 1e300 means "absent" (numeric_limits lowest/max)
-constexpr double kFeasTol = 1e-6;  // CPLEX default feasibility tolerance (CPLEX.cpp:8 default ctor)
-// reduce-kernel statuses beyond qpcpp::SolveStatus: -1 = the PDIP solves it; capacity errors
-constexpr int RS_SOLVE = -1, RS_CAP_NZ = -2, RS_CAP_ROWS = -3;
+// (the limits DENSE_* / DQ_*, kInf, kFeasTol, the RS_* statuses, ET_PAD: host/dense_route.hpp)
+static_assert(DENSE_DAS_ROWS == dev::WROWS, "the route's active-set row limit is the wave PDIP's");
 
 // Packed QP (host -> device; dense_pack.hpp pack_qp). Int words: [n, me, mi, nh | in row ptr
 // (mi + 1, int32) | eq row ptr (me + 1, u16) | Hs index (i << 6 | j, i <= j; nh, u16) | eq cols
@@ -98,17 +90,7 @@ struct DenseBatch {
 
 namespace dev {
 
-// zero rows after the E^T image: the QR's row loops run in unguarded chunks of ET_PAD rows (16
-// took the kernel to 141 registers, three waves per SIMD, for no gain in the QR)
-constexpr int ET_PAD = 8;
-
-// E^T / H image in dynamic LDS, sized per batch: rows = the batch's largest n, row stride S = the
-// larger of its largest n and equality count, made odd (spread banks); at most 64 x 65 doubles
-__host__ __device__ inline int reduce_stride(int nmax, int emax) {
-    const int s = nmax > emax ? nmax : emax;
-    return s | 1;
-}
-
+// (the E^T / H image in dynamic LDS: a.lds_rows + ET_PAD rows of stride a.lds_stride, dense_route.hpp)
 struct ReduceLds {
     double z[DENSE_NMAX * DENSE_NZ]; // Z row-major
     double xp[DENSE_NMAX];
@@ -725,10 +707,16 @@ __global__ void __launch_bounds__(64) dense_expand_kernel(const DenseBatch a) {
 
 namespace {
 
-struct DevBuf {
+using dense_pack::PackPlan;
+using dense_pack::plan_qp;
+using dense_route::Section;
+
+// The three buffers of a call, kept per thread across calls and never freed (no destructor:
+// freeing after the HIP runtime's own teardown is unsafe); sections by dense_route::DenseLayout.
+struct DenseDevBuf {
     void* p = nullptr;
     size_t bytes = 0;
-    int device = -1;  // no destructor: freeing after the HIP runtime's own teardown is unsafe
+    int device = -1;  // the device it was allocated on
     hipError_t reserve(size_t need, int dev) {
         if (p && bytes >= need && device == dev) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -741,8 +729,10 @@ struct DevBuf {
         }
         return e;
     }
+    template <typename T>
+    T* dev(Section s) const { return dense_route::section_ptr<T>(p, s); }
 };
-struct HostBuf {  // pinned (page-locked, device-mapped) host memory the kernels read / write
+struct DensePinnedBuf {  // pinned (page-locked, device-mapped) host memory the kernels read / write
     void* p = nullptr;
     void* dp = nullptr;  // the device's pointer to it
     size_t bytes = 0;
@@ -757,21 +747,14 @@ struct HostBuf {  // pinned (page-locked, device-mapped) host memory the kernels
         if (e == hipSuccess) bytes = need;
         return e;
     }
-    // device address of a host address inside the buffer
     template <typename T>
-    T* dev(const void* h) const { return (T*)((char*)dp + ((const char*)h - (const char*)p)); }
+    T* host(Section s) const { return dense_route::section_ptr<T>(p, s); }
+    template <typename T>
+    T* dev(Section s) const { return dense_route::section_ptr<T>(dp, s); }  // the same bytes, as the device addresses them
 };
-thread_local DevBuf g_dense_buf;
-thread_local HostBuf g_dense_host;
-thread_local HostBuf g_dense_out;  // pinned x | obj | status of the last call
-
-size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
-
-static_assert(dense_pack::DENSE_NMAX == DENSE_NMAX && dense_pack::DENSE_EMAX == DENSE_EMAX &&
-              dense_pack::kInf == kInf, "dense_pack.hpp and dense_qp.hip agree");
-using dense_pack::finite_bound;
-using dense_pack::PackPlan;
-using dense_pack::plan_qp;
+thread_local DenseDevBuf g_dense_buf;
+thread_local DensePinnedBuf g_dense_host;  // the packed input
+thread_local DensePinnedBuf g_dense_out;   // x | obj | status of the last call
 
 // Host worker pool for the per-QP validation and packing: created on first use (up to 15 workers
 // beside the calling thread), kept for the process (a thread spawn per call cost more than the
@@ -849,6 +832,293 @@ void parallel_for(int count, F f) {
     PackPool::get().run(count, fn);
 }
 
+// ---- one mpccbf_qp_solve_dense_batch call: what its steps share, then the steps in call order.
+// The route (slices, LDS geometry, launches) and the buffers' layout come from dense_route.hpp.
+struct DenseCall {
+    const int32_t count;
+    const mpccbf_dense_qp* const qps;
+    // each QP's slot in the packed doubles / ints (with the totals at [count]) and the reduced QPs
+    std::vector<int64_t> off_d, off_i, red_off;
+    dense_route::DenseLayout lay;
+    DenseBatch a;
+    hipStream_t s = nullptr;
+    std::vector<PackPlan> plan;
+    std::vector<dense_route::QpShape> shape;
+    // QPs beyond the device elimination (more than 64 variables or 64 equality rows): the equality
+    // elimination on the host (host/dense_qp.cpp, after the slices), the reduced QP solved on the
+    // device like the rest, x expanded on the host
+    std::vector<int> big;
+    std::vector<ReducedQP> hred;
+    std::vector<ReducedBlock> hblk;
+    std::vector<double> yb;                 // their y (DENSE_NZ each)
+    std::vector<std::vector<double>> xbig;  // their x (OPTIMAL ones)
+    DenseCall(int32_t n, const mpccbf_dense_qp* q)
+        : count(n), qps(q), off_d(n + 1), off_i(n + 1), red_off(n), plan(n), shape(n) {}
+};
+
+#define DENSE_STEP(expr)                    \
+    do {                                    \
+        const int rc_ = (expr);             \
+        if (rc_ != MPCCBF_OK) return rc_;   \
+    } while (0)
+
+int hip_error(const char* what, hipError_t e) {
+    return e == hipSuccess ? MPCCBF_OK : set_error(MPCCBF_ERR_HIP, std::string(what) + hipGetErrorString(e));
+}
+int solve_error(hipError_t e) { return hip_error("dense QP solve: ", e); }
+int qp_error(int k, const std::string& msg) {
+    return set_error(MPCCBF_ERR_INVALID_ARGUMENT, "QP " + std::to_string(k) + ": " + msg);
+}
+
+// Every QP's slot from n and m alone (an upper bound of its packed size: no sizing pass over H and
+// A before the packing pass); returns the totals.
+dense_route::SlotBound size_slots(DenseCall& c) {
+    dense_route::SlotBound t;
+    for (int k = 0; k < c.count; k++) {
+        c.off_d[k] = (int64_t)t.nd;
+        c.off_i[k] = (int64_t)t.ni;
+        c.red_off[k] = (int64_t)t.nred;
+        const dense_route::SlotBound b = dense_route::slot_bound(c.qps[k].n, c.qps[k].m);
+        t.nd += b.nd;
+        t.ni += b.ni;
+        t.nred += b.nred;
+    }
+    c.off_d[c.count] = (int64_t)t.nd;
+    c.off_i[c.count] = (int64_t)t.ni;
+    return t;
+}
+
+// no device: the QPs' own argument errors still take precedence, as a host-side check
+int no_device_error(const DenseCall& c) {
+    for (int k = 0; k < c.count; k++) {
+        const PackPlan pl = plan_qp(c.qps[k]);
+        if (!pl.err.empty()) return qp_error(k, pl.err);
+    }
+    return set_error(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+}
+
+// The three buffers at this call's sizes (grown when too small), the slots' offsets into the
+// pinned input.
+int reserve_buffers(DenseCall& c, const dense_route::SlotBound& total) {
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    c.lay = dense_route::dense_layout((size_t)c.count, total.nd, total.ni, total.nred);
+    if (e == hipSuccess) e = g_dense_host.reserve(c.lay.in_bytes);
+    if (e == hipSuccess) e = g_dense_out.reserve(c.lay.out_bytes);
+    DENSE_STEP(hip_error("dense QP staging: ", e));
+    std::memcpy(g_dense_host.host<int64_t>(c.lay.off_d), c.off_d.data(), (c.count + 1) * sizeof(int64_t));
+    std::memcpy(g_dense_host.host<int64_t>(c.lay.off_i), c.off_i.data(), (c.count + 1) * sizeof(int64_t));
+    std::memcpy(g_dense_host.host<int64_t>(c.lay.red_off), c.red_off.data(), c.count * sizeof(int64_t));
+    return hip_error("dense QP buffers: ", g_dense_buf.reserve(c.lay.dev_bytes, device));
+}
+
+// The kernels' argument: every section's device address, the solver's settings.
+DenseBatch batch_args(const dense_route::DenseLayout& l, int32_t count) {
+    DenseBatch a;
+    a.dbl = g_dense_host.dev<const double>(l.dbl);
+    a.ints = g_dense_host.dev<const int32_t>(l.ints);
+    a.off_d = g_dense_host.dev<const int64_t>(l.off_d);
+    a.off_i = g_dense_host.dev<const int64_t>(l.off_i);
+    a.red_off = g_dense_host.dev<const int64_t>(l.red_off);
+    a.hostred = g_dense_host.dev<const int32_t>(l.hostred);
+    a.psize = g_dense_host.dev<const int32_t>(l.psize);
+    a.count = count;
+    a.red = g_dense_buf.dev<double>(l.red);
+    a.zx = g_dense_buf.dev<double>(l.zx);
+    a.y = g_dense_buf.dev<double>(l.y);
+    a.status = g_dense_buf.dev<int32_t>(l.status);
+    a.m = g_dense_buf.dev<int32_t>(l.m);
+    a.pd = g_dense_buf.dev<int32_t>(l.pd);
+    a.iters = g_dense_buf.dev<int32_t>(l.iters);
+    a.x = g_dense_out.dev<double>(l.x);
+    a.obj = g_dense_out.dev<double>(l.obj);
+    a.status_out = g_dense_out.dev<int32_t>(l.status_out);
+    a.maxit = kDenseMaxIt;
+    a.das_steps = kDenseDasSteps;
+    a.tol = kDenseTol;
+    a.feas_tol = kFeasTol;
+    a.lds_rows = a.lds_stride = a.stage_d = a.stage_i = a.first = 0;  // (per slice: launch_reduction)
+    a.dstamps = nullptr;
+    return a;
+}
+
+// profiling build: QP 0's reduction phases, printed to stderr with MPCCBF_DENSE_STAMPS=1
+void attach_stamps(DenseBatch& a) {
+#ifdef MPCCBF_PDIP_STAMPS
+    static long long* d_stamps = nullptr;
+    const bool want_stamps = std::getenv("MPCCBF_DENSE_STAMPS") != nullptr;
+    if (want_stamps && !d_stamps && hipMalloc(&d_stamps, 24 * sizeof(long long)) != hipSuccess) d_stamps = nullptr;
+    if (want_stamps && d_stamps) {
+        (void)hipMemset(d_stamps, 0, 24 * sizeof(long long));
+        a.dstamps = d_stamps;
+    }
+#endif
+}
+void print_stamps(const DenseBatch& a) {
+#ifdef MPCCBF_PDIP_STAMPS
+    long long h[24];
+    if (!a.dstamps || hipMemcpy(h, a.dstamps, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
+    std::fprintf(stderr, "dense_stamps");
+    for (int k = 1; k <= 10; k++) std::fprintf(stderr, " %lld", h[k] - h[k - 1]);
+    std::fprintf(stderr, " | t10: %lld", h[11] - h[16]);
+    std::fprintf(stderr, " (w loop %lld)", h[17] - h[14]);
+    for (int k = 12; k <= 15; k++) std::fprintf(stderr, " %lld", h[k] - h[k - 1]);
+    std::fprintf(stderr, "\n");
+#endif
+}
+
+// Validation, row classification and the packed form of QPs [q0, q1), one pass per QP on the
+// worker pool, written straight into the pinned input (the kernels read it there: no copy).
+void pack_slice(DenseCall& c, int q0, int q1) {
+    double* h_d = g_dense_host.host<double>(c.lay.dbl);
+    int32_t* h_i = g_dense_host.host<int32_t>(c.lay.ints);
+    int32_t* h_hr = g_dense_host.host<int32_t>(c.lay.hostred);
+    int32_t* h_ps = g_dense_host.host<int32_t>(c.lay.psize);
+    parallel_for(q1 - q0, [&](int k0, int k1) {
+        thread_local dense_pack::PackScratch scratch;
+        for (int k = q0 + k0; k < q0 + k1; k++) {
+            c.plan[k] = dense_pack::pack_qp_once(c.qps[k], h_d + c.off_d[k], h_i + c.off_i[k], scratch);
+            const PackPlan& pl = c.plan[k];
+            const bool packed = pl.err.empty() && !pl.cap;
+            c.shape[k] = dense_pack::shape_of(pl);
+            h_hr[k] = pl.cap ? 1 : 0;
+            h_ps[2 * k] = packed ? (int32_t)pl.nd + dense_route::PACK_SPARE : 0;  // (the spare word is staged too)
+            h_ps[2 * k + 1] = packed ? (int32_t)pl.ni + dense_route::PACK_SPARE : 0;
+        }
+    });
+}
+
+// The first bad QP of the slice, as a serial pass would report it (the slices before it are
+// finished first: the pinned input stays theirs until then).
+int first_bad_qp(const DenseCall& c, int q0, int q1) {
+    for (int k = q0; k < q1; k++)
+        if (!c.plan[k].err.empty()) {
+            (void)hipStreamSynchronize(c.s);
+            return qp_error(k, c.plan[k].err);
+        }
+    return MPCCBF_OK;
+}
+
+// The slice's reduction, sized by the slice's own largest QP; the host packs the next meanwhile.
+int launch_reduction(DenseCall& c, int q0, int q1) {
+    const dense_route::SliceRoute r = dense_route::slice_route(c.shape.data(), q0, q1);
+    c.a.lds_rows = r.lds_rows;
+    c.a.lds_stride = r.lds_stride;
+    c.a.stage_d = r.stage_d;
+    c.a.stage_i = r.stage_i;
+    c.a.first = q0;
+    hipLaunchKernelGGL(dev::dense_reduce_kernel, dim3(q1 - q0), dim3(64), r.lds_bytes, c.s, c.a);
+    return solve_error(hipGetLastError());
+}
+
+// The host-reduced QPs' elimination; their reduced row counts into the shapes.
+int reduce_on_host(DenseCall& c) {
+    c.big = dense_route::host_reduced(c.shape.data(), c.count);
+    c.hred.resize(c.big.size());
+    for (size_t b = 0; b < c.big.size(); b++) {
+        try {
+            c.hred[b] = reduce_dense_qp(c.qps[c.big[b]]);
+        } catch (const std::exception& ex) {
+            (void)hipStreamSynchronize(c.s);
+            return qp_error(c.big[b], ex.what());
+        }
+        c.shape[c.big[b]].rows = c.hred[b].m;
+    }
+    return MPCCBF_OK;
+}
+
+// Their reduced form and the reduction's decision, where the device reduction leaves its own.
+int upload_host_reduced(DenseCall& c) {
+    c.hblk.resize(c.big.size());
+    hipError_t e = hipSuccess;
+    for (size_t b = 0; b < c.big.size() && e == hipSuccess; b++) {
+        const ReducedBlock& blk = c.hblk[b] = device_block(c.hred[b]);
+        const int k = c.big[b];
+        e = hipMemcpyAsync(c.a.red + c.red_off[k], blk.dbl.data(), blk.dbl.size() * sizeof(double),
+                           hipMemcpyHostToDevice, c.s);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.a.status + k, &blk.status, sizeof(int32_t), hipMemcpyHostToDevice, c.s);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.a.m + k, &blk.m, sizeof(int32_t), hipMemcpyHostToDevice, c.s);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.a.pd + k, &blk.pd, sizeof(int32_t), hipMemcpyHostToDevice, c.s);
+    }
+    return solve_error(e);
+}
+
+// The active-set launch (when the route has one) and, where the early exit is possible, whether
+// it settled every QP: the pinned statuses after one synchronisation.
+int run_active_set(DenseCall& c, const dense_route::CallRoute& route, bool* settled) {
+    *settled = false;
+    if (!route.active_set) return MPCCBF_OK;
+    hipLaunchKernelGGL((dev::dense_das_kernel<DENSE_NZ>), dim3(c.count), dim3(64), 0, c.s, c.a);
+    DENSE_STEP(solve_error(hipGetLastError()));
+    if (!route.early_exit) return MPCCBF_OK;
+    DENSE_STEP(solve_error(hipStreamSynchronize(c.s)));
+    const int32_t* so = g_dense_out.host<const int32_t>(c.lay.status_out);
+    *settled = true;
+    for (int k = 0; k < c.count && *settled; k++) *settled = so[k] != RS_SOLVE;
+    return MPCCBF_OK;
+}
+
+int run_pdip_and_expansion(DenseCall& c, const dense_route::CallRoute& route) {
+    const dim3 grid(c.count), block(64);
+    if (route.R == 1) hipLaunchKernelGGL((dev::dense_qp_kernel<DENSE_NZ, 1>), grid, block, 0, c.s, c.a);
+    else if (route.R == 2) hipLaunchKernelGGL((dev::dense_qp_kernel<DENSE_NZ, 2>), grid, block, 0, c.s, c.a);
+    else hipLaunchKernelGGL((dev::dense_qp_kernel<DENSE_NZ, DQ_R>), grid, block, 0, c.s, c.a);
+    DENSE_STEP(solve_error(hipGetLastError()));
+    hipLaunchKernelGGL(dev::dense_expand_kernel, grid, block, 0, c.s, c.a);
+    return solve_error(hipGetLastError());
+}
+
+// The host-reduced QPs' y back, then the end of the stream's work.
+int synchronise(DenseCall& c) {
+    c.yb.resize(c.big.size() * DENSE_NZ);
+    hipError_t e = hipSuccess;
+    for (size_t b = 0; b < c.big.size() && e == hipSuccess; b++)
+        e = hipMemcpyAsync(&c.yb[b * DENSE_NZ], c.a.y + (size_t)c.big[b] * DENSE_NZ, DENSE_NZ * sizeof(double),
+                           hipMemcpyDeviceToHost, c.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.s);
+    if (e == hipSuccess) print_stamps(c.a);
+    return solve_error(e);
+}
+
+// host-reduced QPs: x = xp + Z y and the full-space objective (into the pinned output)
+void expand_host_reduced(DenseCall& c) {
+    const int32_t* st = g_dense_out.host<const int32_t>(c.lay.status_out);
+    double* obj = g_dense_out.host<double>(c.lay.obj);
+    c.xbig.resize(c.big.size());
+    for (size_t b = 0; b < c.big.size(); b++) {
+        const int k = c.big[b];
+        if (st[k] != MPCCBF_OPTIMAL) continue;
+        c.xbig[b].resize(c.qps[k].n);
+        expand_solution(c.hred[b], &c.yb[b * DENSE_NZ], c.xbig[b].data(), &obj[k]);
+    }
+}
+
+// capacity errors are the call's error only after the solve, the lowest k first
+int capacity_error(const DenseCall& c) {
+    const int32_t* st = g_dense_out.host<const int32_t>(c.lay.status_out);
+    for (int k = 0; k < c.count; k++)
+        if (st[k] == RS_CAP_NZ || st[k] == RS_CAP_ROWS)
+            return set_error(MPCCBF_ERR_CAPACITY, "QP " + std::to_string(k) +
+                                                      (st[k] == RS_CAP_NZ ? ": reduced dimension exceeds 8"
+                                                                          : ": reduced rows exceed 256"));
+    return MPCCBF_OK;
+}
+
+// outputs: x only for OPTIMAL (Solver.h:33-35), the objective NaN otherwise
+void copy_out(const DenseCall& c, double* const* x_out, double* obj_out, int32_t* status_out) {
+    const double* x = g_dense_out.host<const double>(c.lay.x);
+    const double* obj = g_dense_out.host<const double>(c.lay.obj);
+    const int32_t* st = g_dense_out.host<const int32_t>(c.lay.status_out);
+    size_t bi = 0;
+    for (int k = 0; k < c.count; k++) {
+        status_out[k] = st[k];
+        if (obj_out) obj_out[k] = st[k] == MPCCBF_OPTIMAL ? obj[k] : __builtin_nan("");
+        const double* xs = &x[(size_t)k * DENSE_NMAX];
+        if (c.shape[k].cap) xs = c.xbig[bi++].data();
+        if (st[k] == MPCCBF_OPTIMAL && x_out && x_out[k]) std::memcpy(x_out[k], xs, (size_t)c.qps[k].n * sizeof(double));
+    }
+}
+
 }  // namespace
 }  // namespace mpccbf
 
@@ -861,286 +1131,32 @@ int mpccbf_qp_solve_dense_batch(int32_t count, const mpccbf_dense_qp* qps, doubl
     if (count < 0 || (count > 0 && (!qps || !status_out)))
         return set_error(MPCCBF_ERR_INVALID_ARGUMENT, "dense QP batch: null argument");
     if (count == 0) return MPCCBF_OK;
-    // ---- host, one pass per QP (worker pool, slice by slice ahead of each slice's reduction):
-    // validation, row classification and the packed form written straight into the pinned input,
-    // at an offset sized beforehand from n and m alone (an upper bound of the packed size: no
-    // separate sizing pass over H and A). The kernels read it there over the bus: no copy
-    std::vector<int64_t> off_d(count + 1), off_i(count + 1), red_off(count);
-    size_t nd = 0, ni = 0, nred = 0;
-    for (int k = 0; k < count; k++) {
-        off_d[k] = (int64_t)nd;
-        off_i[k] = (int64_t)ni;
-        red_off[k] = (int64_t)nred;
-        const int64_t n = qps[k].n, m = qps[k].m;
-        const bool packable = n >= 1 && n <= DENSE_NMAX && m >= 0;
-        if (packable) {  // (the sizes of pack_qp with nh <= n (n + 1) / 2, me + mi <= m + n, enz + inz <= m n + n)
-            const int64_t hmax = n * (n + 1) / 2, rows = m + n, nzmax = m * n + n;
-            nd += (size_t)(n + 1 + hmax + 2 * rows + nzmax) + 1;  // (+1: the spare word of pack_qp's compaction)
-            ni += (size_t)(4 + (rows + 1) + (2 * (rows + 1) + 2 * hmax + nzmax + 3) / 4) + 1;
-        }
-        // reduced-QP block: its reduced rows are a subset of the inequality rows (<= m + n); a QP
-        // with more than DENSE_ROWS is a capacity error before its rows are read
-        const int64_t rows_k = (n >= 1 && m >= 0) ? std::min<int64_t>(m + n, DENSE_ROWS) : 1;
-        nred += (size_t)DQ_HDR + (size_t)std::max<int64_t>(rows_k, 1) * DQ_ROW;  // (>= 1 row: the kernel reads row 0)
-    }
-    off_d[count] = (int64_t)nd;
-    off_i[count] = (int64_t)ni;
+    DenseCall c(count, qps);
+    const dense_route::SlotBound total = size_slots(c);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        // (no device: the QPs' own argument errors still take precedence, as a host-side check)
-        for (int k = 0; k < count; k++) {
-            const PackPlan pl = plan_qp(qps[k]);
-            if (!pl.err.empty()) return set_error(MPCCBF_ERR_INVALID_ARGUMENT, "QP " + std::to_string(k) + ": " + pl.err);
-        }
-        return set_error(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return no_device_error(c);
+    DENSE_STEP(reserve_buffers(c, total));
+    c.a = batch_args(c.lay, count);
+    attach_stamps(c.a);
+    // slice by slice: the device reduces one slice while the host packs the next
+    const dense_route::Slices slices = dense_route::slices_of(count);
+    for (int i = 0; i < slices.n; i++) {
+        const int q0 = slices.q0[i], q1 = slices.q0[i + 1];
+        pack_slice(c, q0, q1);
+        DENSE_STEP(first_bad_qp(c, q0, q1));
+        DENSE_STEP(launch_reduction(c, q0, q1));
     }
-    int device = 0;
-    hipError_t e = hipGetDevice(&device);
-    // ---- pinned input: packed doubles | packed ints | off_d | off_i | red_off | host-reduced
-    // flags | packed sizes (2 per QP); pinned output: x | obj | status
-    const size_t b_d = align16(nd * sizeof(double)), b_i = align16(ni * sizeof(int32_t));
-    const size_t b_off = align16((size_t)(count + 1) * sizeof(int64_t));
-    const size_t b_int = align16((size_t)count * sizeof(int32_t));
-    const size_t b_ps = align16((size_t)count * 2 * sizeof(int32_t));
-    const size_t in_bytes = b_d + b_i + 3 * b_off + b_int + b_ps;
-    const size_t b_x = align16((size_t)count * DENSE_NMAX * sizeof(double));
-    const size_t b_obj = align16((size_t)count * sizeof(double));
-    if (e == hipSuccess) e = g_dense_host.reserve(in_bytes);
-    if (e == hipSuccess) e = g_dense_out.reserve(b_x + b_obj + b_int);
-    if (e != hipSuccess) return set_error(MPCCBF_ERR_HIP, std::string("dense QP staging: ") + hipGetErrorString(e));
-    char* hb = (char*)g_dense_host.p;
-    double* h_d = (double*)hb;
-    int32_t* h_i = (int32_t*)(hb + b_d);
-    int64_t* h_offd = (int64_t*)(hb + b_d + b_i);
-    int64_t* h_offi = (int64_t*)(hb + b_d + b_i + b_off);
-    int64_t* h_redoff = (int64_t*)(hb + b_d + b_i + 2 * b_off);
-    int32_t* h_hr = (int32_t*)(hb + b_d + b_i + 3 * b_off);
-    int32_t* h_ps = (int32_t*)(hb + b_d + b_i + 3 * b_off + b_int);
-    std::memcpy(h_offd, off_d.data(), (count + 1) * sizeof(int64_t));
-    std::memcpy(h_offi, off_i.data(), (count + 1) * sizeof(int64_t));
-    std::memcpy(h_redoff, red_off.data(), count * sizeof(int64_t));
-    // ---- device buffers: reduced QPs | Z, xp | y | status | m | pd | iters
-    const size_t b_red = align16(nred * sizeof(double));
-    const size_t b_zx = align16((size_t)count * (DENSE_NMAX * DENSE_NZ + DENSE_NMAX) * sizeof(double));
-    const size_t b_y = align16((size_t)count * DENSE_NZ * sizeof(double));
-    e = g_dense_buf.reserve(b_red + b_zx + b_y + 4 * b_int, device);
-    if (e != hipSuccess) return set_error(MPCCBF_ERR_HIP, std::string("dense QP buffers: ") + hipGetErrorString(e));
-    char* p = (char*)g_dense_buf.p;
-    DenseBatch a;
-    a.dbl = g_dense_host.dev<const double>(h_d);
-    a.ints = g_dense_host.dev<const int32_t>(h_i);
-    a.off_d = g_dense_host.dev<const int64_t>(h_offd);
-    a.off_i = g_dense_host.dev<const int64_t>(h_offi);
-    a.red_off = g_dense_host.dev<const int64_t>(h_redoff);
-    a.hostred = g_dense_host.dev<const int32_t>(h_hr);
-    a.psize = g_dense_host.dev<const int32_t>(h_ps);
-    a.count = count;
-    a.red = (double*)p;
-    p += b_red;
-    a.zx = (double*)p;
-    p += b_zx;
-    a.y = (double*)p;
-    p += b_y;
-    a.status = (int32_t*)p;
-    a.m = (int32_t*)(p + b_int);
-    a.pd = (int32_t*)(p + 2 * b_int);
-    a.iters = (int32_t*)(p + 3 * b_int);
-    char* ho = (char*)g_dense_out.p;
-    a.x = g_dense_out.dev<double>(ho);
-    a.obj = g_dense_out.dev<double>(ho + b_x);
-    a.status_out = g_dense_out.dev<int32_t>(ho + b_x + b_obj);
-    a.maxit = 100;
-    a.das_steps = 48;
-    a.tol = 1e-9;
-    a.feas_tol = 1e-6;
-    a.dstamps = nullptr;
-#ifdef MPCCBF_PDIP_STAMPS
-    // profiling build: QP 0's reduction phases, printed to stderr with MPCCBF_DENSE_STAMPS=1
-    static long long* d_stamps = nullptr;
-    const bool want_stamps = std::getenv("MPCCBF_DENSE_STAMPS") != nullptr;
-    if (want_stamps && !d_stamps && hipMalloc(&d_stamps, 24 * sizeof(long long)) != hipSuccess) d_stamps = nullptr;
-    if (want_stamps && d_stamps) {
-        (void)hipMemset(d_stamps, 0, 24 * sizeof(long long));
-        a.dstamps = d_stamps;
-    }
-#endif
-    hipStream_t s = nullptr;
-    std::vector<PackPlan> plan(count);
-    // QPs beyond the device elimination (more than 64 variables or 64 equality rows): the equality
-    // elimination on the host (host/dense_qp.cpp, after the slices), the reduced QP solved on the
-    // device like the rest
-    std::vector<int> big;
-    int rows_max = 1;
-    // validate + pack a slice (worker pool), launch its reduction (sized by the slice's own
-    // largest QP), pack the next meanwhile; the first bad QP's error as a serial pass would report
-    // it (the slices before it are finished first: the pinned input stays theirs until then)
-    const int nslice = count >= 1024 ? 4 : 1;
-    const int slice = (count + nslice - 1) / nslice;
-    for (int q0 = 0; q0 < count && e == hipSuccess; q0 += slice) {
-        const int q1 = std::min(count, q0 + slice);
-        parallel_for(q1 - q0, [&](int k0, int k1) {
-            thread_local dense_pack::PackScratch scratch;
-            for (int k = q0 + k0; k < q0 + k1; k++) {
-                plan[k] = dense_pack::pack_qp_once(qps[k], h_d + off_d[k], h_i + off_i[k], scratch);
-                const PackPlan& pl = plan[k];
-                const bool packed = pl.err.empty() && !pl.cap;
-                h_hr[k] = pl.cap ? 1 : 0;
-                h_ps[2 * k] = packed ? (int32_t)pl.nd + 1 : 0;  // (+1: the spare word, staged as before)
-                h_ps[2 * k + 1] = packed ? (int32_t)pl.ni + 1 : 0;
-            }
-        });
-        int nmax = 1, emax = 1, sd_max = 0, si_max = 0;
-        for (int k = q0; k < q1; k++) {
-            if (!plan[k].err.empty()) {
-                (void)hipStreamSynchronize(s);
-                return set_error(MPCCBF_ERR_INVALID_ARGUMENT, "QP " + std::to_string(k) + ": " + plan[k].err);
-            }
-            if (plan[k].cap) {
-                big.push_back(k);
-                continue;
-            }
-            rows_max = std::max(rows_max, std::min(plan[k].mi, DENSE_ROWS));
-            nmax = std::max(nmax, plan[k].n);
-            emax = std::max(emax, plan[k].me);
-            sd_max = std::max(sd_max, (int)plan[k].nd + 1);
-            si_max = std::max(si_max, (int)plan[k].ni + 1);
-        }
-        a.lds_rows = nmax;
-        a.lds_stride = dev::reduce_stride(nmax, emax);
-        size_t lds = (size_t)(a.lds_rows + dev::ET_PAD) * a.lds_stride * sizeof(double);
-        const size_t stage = (size_t)sd_max * sizeof(double) + (size_t)si_max * sizeof(int32_t);
-        a.stage_d = a.stage_i = 0;
-        if (lds + stage <= 48 * 1024) {  // (beyond: the kernel reads its QP over the bus where it uses it)
-            a.stage_d = sd_max;
-            a.stage_i = si_max;
-            lds += stage;
-        }
-        a.first = q0;
-        hipLaunchKernelGGL(dev::dense_reduce_kernel, dim3(q1 - q0), dim3(64), lds, s, a);
-        e = hipGetLastError();
-    }
-    std::vector<ReducedQP> hred(big.size());
-    for (size_t b = 0; b < big.size() && e == hipSuccess; b++) {
-        try {
-            hred[b] = reduce_dense_qp(qps[big[b]]);
-        } catch (const std::exception& ex) {
-            (void)hipStreamSynchronize(s);
-            return set_error(MPCCBF_ERR_INVALID_ARGUMENT, "QP " + std::to_string(big[b]) + ": " + ex.what());
-        }
-        rows_max = std::max(rows_max, std::min(hred[b].m, DENSE_ROWS));
-    }
-    a.first = 0;
-    // host-reduced QPs: their reduced form in the device layout (P, LP padded with the identity, q,
-    // the Newton ridge when P is only semidefinite, rows [g | lo | hi]) and the decision
-    std::vector<std::vector<double>> hblk(big.size());
-    std::vector<int32_t> hst(big.size()), hm(big.size()), hpd(big.size());
-    for (size_t b = 0; b < big.size() && e == hipSuccess; b++) {
-        const ReducedQP& r = hred[b];
-        int st_b = RS_SOLVE;
-        // the device kernel's order (dense_reduce_kernel): inconsistent equalities, then capacity,
-        // then a violated constant row
-        if (r.eq_infeasible) st_b = MPCCBF_INFEASIBLE;
-        else if (r.nz > DENSE_NZ) st_b = RS_CAP_NZ;
-        else if (r.m > DENSE_ROWS) st_b = RS_CAP_ROWS;
-        else if (r.status >= 0) st_b = r.status;  // (a violated constant row; nz = 0: x = xp)
-        std::vector<double>& blk = hblk[b];
-        blk.assign((size_t)DQ_HDR + (size_t)std::min(r.m, DENSE_ROWS) * DQ_ROW, 0.0);
-        double pmax = 0.0;
-        if (st_b == RS_SOLVE) {
-            for (int i = 0; i < DENSE_NZ; i++)
-                for (int j = 0; j < DENSE_NZ; j++) {
-                    const bool in = i < r.nz && j < r.nz;
-                    blk[i * DENSE_NZ + j] = in ? r.P(i, j) : (i == j ? 1.0 : 0.0);
-                    blk[DENSE_NZ * DENSE_NZ + i * DENSE_NZ + j] =
-                        (in && r.pd) ? (j <= i ? r.LP(i, j) : 0.0) : (i == j ? 1.0 : 0.0);
-                    if (in) pmax = std::max(pmax, std::fabs(r.P(i, j)));
-                }
-            for (int i = 0; i < r.nz; i++) blk[2 * DENSE_NZ * DENSE_NZ + i] = r.q[i];
-            blk[2 * DENSE_NZ * DENSE_NZ + DENSE_NZ] = r.pd ? 0.0 : 1e-10 * std::max(1.0, pmax);
-            for (int k = 0; k < r.m && k < DENSE_ROWS; k++) {
-                double* row = &blk[DQ_HDR + (size_t)k * DQ_ROW];
-                for (int j = 0; j < r.nz; j++) row[j] = r.G(k, j);
-                row[DENSE_NZ] = r.lo[k];
-                row[DENSE_NZ + 1] = r.hi[k];
-            }
-        }
-        hst[b] = st_b;
-        hm[b] = std::min(r.m, DENSE_ROWS);
-        hpd[b] = r.pd ? 1 : 0;
-        const int k = big[b];
-        e = hipMemcpyAsync(a.red + red_off[k], blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(a.status + k, &hst[b], sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(a.m + k, &hm[b], sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(a.pd + k, &hpd[b], sizeof(int32_t), hipMemcpyHostToDevice, s);
-    }
-    // the active-set launch settles most QPs and writes their final outputs (and those of the QPs
-    // the reduction decided); a small batch whose QPs it all settled needs no PDIP and no
-    // expansion launch (the host checks the pinned statuses after one synchronisation)
+    c.a.first = 0;
+    DENSE_STEP(reduce_on_host(c));
+    DENSE_STEP(upload_host_reduced(c));
+    const dense_route::CallRoute route = dense_route::call_route(c.shape.data(), count);
     bool settled = false;
-    if (e == hipSuccess && a.das_steps > 0 && rows_max <= dev::WROWS) {
-        hipLaunchKernelGGL((dev::dense_das_kernel<DENSE_NZ>), dim3(count), dim3(64), 0, s, a);
-        e = hipGetLastError();
-        if (e == hipSuccess && count <= 64 && big.empty()) {
-            e = hipStreamSynchronize(s);
-            const int32_t* so = (const int32_t*)(ho + b_x + b_obj);
-            settled = e == hipSuccess;
-            for (int k = 0; k < count && settled; k++) settled = so[k] != RS_SOLVE;
-        }
-    }
-    if (e == hipSuccess && !settled) {
-        if (rows_max <= 64) hipLaunchKernelGGL((dev::dense_qp_kernel<DENSE_NZ, 1>), dim3(count), dim3(64), 0, s, a);
-        else if (rows_max <= 128) hipLaunchKernelGGL((dev::dense_qp_kernel<DENSE_NZ, 2>), dim3(count), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((dev::dense_qp_kernel<DENSE_NZ, DQ_R>), dim3(count), dim3(64), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !settled) {
-        hipLaunchKernelGGL(dev::dense_expand_kernel, dim3(count), dim3(64), 0, s, a);
-        e = hipGetLastError();
-    }
-    std::vector<double> yb(big.size() * DENSE_NZ);
-    for (size_t b = 0; b < big.size() && e == hipSuccess; b++)
-        e = hipMemcpyAsync(&yb[b * DENSE_NZ], a.y + (size_t)big[b] * DENSE_NZ, DENSE_NZ * sizeof(double),
-                           hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-#ifdef MPCCBF_PDIP_STAMPS
-    if (a.dstamps && e == hipSuccess) {
-        long long h[24];
-        if (hipMemcpy(h, a.dstamps, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
-            std::fprintf(stderr, "dense_stamps");
-            for (int k = 1; k <= 10; k++) std::fprintf(stderr, " %lld", h[k] - h[k - 1]);
-            std::fprintf(stderr, " | t10: %lld", h[11] - h[16]);
-            std::fprintf(stderr, " (w loop %lld)", h[17] - h[14]);
-            for (int k = 12; k <= 15; k++) std::fprintf(stderr, " %lld", h[k] - h[k - 1]);
-            std::fprintf(stderr, "\n");
-        }
-    }
-#endif
-    if (e != hipSuccess) return set_error(MPCCBF_ERR_HIP, std::string("dense QP solve: ") + hipGetErrorString(e));
-    const double* x = (const double*)ho;
-    double* obj = (double*)(ho + b_x);
-    const int32_t* st = (const int32_t*)(ho + b_x + b_obj);
-    // host-reduced QPs: x = xp + Z y and the full-space objective
-    std::vector<std::vector<double>> xbig(big.size());
-    for (size_t b = 0; b < big.size(); b++) {
-        const int k = big[b];
-        if (st[k] != MPCCBF_OPTIMAL) continue;
-        xbig[b].resize(qps[k].n);
-        expand_solution(hred[b], &yb[b * DENSE_NZ], xbig[b].data(), &obj[k]);
-    }
-    for (int k = 0; k < count; k++)
-        if (st[k] == RS_CAP_NZ || st[k] == RS_CAP_ROWS)
-            return set_error(MPCCBF_ERR_CAPACITY, "QP " + std::to_string(k) +
-                                                      (st[k] == RS_CAP_NZ ? ": reduced dimension exceeds 8"
-                                                                          : ": reduced rows exceed 256"));
-    // outputs: x only for OPTIMAL (Solver.h:33-35)
-    size_t bi = 0;
-    for (int k = 0; k < count; k++) {
-        status_out[k] = st[k];
-        if (obj_out) obj_out[k] = st[k] == MPCCBF_OPTIMAL ? obj[k] : __builtin_nan("");
-        const double* xs = &x[(size_t)k * DENSE_NMAX];
-        if (plan[k].cap) xs = xbig[bi++].data();
-        if (st[k] == MPCCBF_OPTIMAL && x_out && x_out[k]) std::memcpy(x_out[k], xs, (size_t)qps[k].n * sizeof(double));
-    }
+    DENSE_STEP(run_active_set(c, route, &settled));
+    if (!settled) DENSE_STEP(run_pdip_and_expansion(c, route));
+    DENSE_STEP(synchronise(c));
+    expand_host_reduced(c);
+    DENSE_STEP(capacity_error(c));
+    copy_out(c, x_out, obj_out, status_out);
     return MPCCBF_OK;
 }
 

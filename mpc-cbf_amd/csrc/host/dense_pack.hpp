@@ -1,6 +1,7 @@
 // dense_pack.hpp — host half of the generic dense QP path (dense_qp.hip): validation of one
 // mpccbf_dense_qp (the reference's invalid_argument cases) and its packed form for the device
-// (layout: dense_qp.hip DenseBatch). Header-only so tools/dense_pack_bench.cpp times the same code.
+// (layout: dense_qp.hip DenseBatch; limits and packed sizes: dense_route.hpp). Header-only so
+// tools/dense_pack_bench.cpp times the same code.
 #pragma once
 
 #include <cfloat>
@@ -11,13 +12,10 @@
 #include <vector>
 
 #include "../../../include/mpccbf.h"
+#include "dense_route.hpp"
 
 namespace mpccbf {
 namespace dense_pack {
-
-constexpr double kInf = 1e300;  // |bound| >= 1e300 means "absent" (numeric_limits lowest/max)
-constexpr int DENSE_NMAX = 64;  // variables per QP on the device elimination (lane = variable)
-constexpr int DENSE_EMAX = 64;  // equalities per QP on the device elimination
 
 inline bool finite_bound(double v) { return std::isfinite(v) && std::fabs(v) < kInf; }
 
@@ -36,6 +34,18 @@ struct PackPlan {
     std::string err;
     bool cap = false;
 };
+
+// what the launch route reads of a plan (a host-reduced QP's rows follow from its reduction)
+inline dense_route::QpShape shape_of(const PackPlan& pl) {
+    dense_route::QpShape s;
+    s.n = pl.n;
+    s.me = pl.me;
+    s.rows = pl.mi;
+    s.nd = pl.nd;
+    s.ni = pl.ni;
+    s.cap = pl.cap;
+    return s;
+}
 
 inline PackPlan plan_qp(const mpccbf_dense_qp& qp) {
     PackPlan pl;
@@ -88,9 +98,8 @@ inline PackPlan plan_qp(const mpccbf_dense_qp& qp) {
     }
     pl.cap = n > DENSE_NMAX || pl.me > DENSE_EMAX;
     if (pl.cap) return pl;  // (reduced on the host: not packed)
-    // int32 words: header, inequality row pointers, then the u16 / u8 arrays (pack_qp)
-    pl.ni = 4 + (size_t)(pl.mi + 1) + (2 * (size_t)(pl.me + 1) + 2 * (size_t)pl.nh + pl.enz + pl.inz + 3) / 4;
-    pl.nd = (size_t)n + 1 + pl.nh + pl.me + pl.enz + 2 * (size_t)pl.mi + pl.inz;
+    pl.ni = dense_route::packed_ints(pl.nh, pl.me, pl.enz, pl.mi, pl.inz);
+    pl.nd = dense_route::packed_doubles(n, pl.nh, pl.me, pl.enz, pl.mi, pl.inz);
     return pl;
 }
 
@@ -294,8 +303,8 @@ inline PackPlan pack_qp_once(const mpccbf_dense_qp& qp, double* db, int32_t* ib,
     pl.inz = rz;
     pl.cap = pl.me > DENSE_EMAX;
     if (pl.cap) return pl;  // (reduced on the host: not packed)
-    pl.ni = 4 + (size_t)(pl.mi + 1) + (2 * (size_t)(pl.me + 1) + 2 * (size_t)pl.nh + pl.enz + pl.inz + 3) / 4;
-    pl.nd = (size_t)n + 1 + pl.nh + pl.me + pl.enz + 2 * (size_t)pl.mi + pl.inz;
+    pl.ni = dense_route::packed_ints(pl.nh, pl.me, pl.enz, pl.mi, pl.inz);
+    pl.nd = dense_route::packed_doubles(n, pl.nh, pl.me, pl.enz, pl.mi, pl.inz);
     // the sections into place (pack_qp's layout)
     ib[0] = n;
     ib[1] = pl.me;

@@ -5,12 +5,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "dense_route.hpp"
+
 namespace mpccbf {
 
 namespace {
-
-constexpr double kInf = 1e300;       // |bound| >= 1e300 means "absent" (numeric_limits lowest/max)
-constexpr double kFeasTol = 1e-6;    // CPLEX default feasibility tolerance (CPLEX.cpp:8 default ctor)
 
 bool finite_bound(double v) { return std::isfinite(v) && std::fabs(v) < kInf; }
 
@@ -171,6 +170,39 @@ void expand_solution(const ReducedQP& r, const double* y, double* x, double* obj
         f += x[i] * (hxi + r.c[i]);
     }
     *obj = f;
+}
+
+ReducedBlock device_block(const ReducedQP& r) {
+    ReducedBlock b;
+    b.status = RS_SOLVE;
+    if (r.eq_infeasible) b.status = MPCCBF_INFEASIBLE;
+    else if (r.nz > DENSE_NZ) b.status = RS_CAP_NZ;
+    else if (r.m > DENSE_ROWS) b.status = RS_CAP_ROWS;
+    else if (r.status >= 0) b.status = r.status;  // (a violated constant row; nz = 0: x = xp)
+    b.m = std::min(r.m, DENSE_ROWS);
+    b.pd = r.pd ? 1 : 0;
+    b.dbl.assign((size_t)DQ_HDR + (size_t)b.m * DQ_ROW, 0.0);
+    if (b.status != RS_SOLVE) return b;
+    double* P = b.dbl.data();
+    double* LP = P + DENSE_NZ * DENSE_NZ;
+    double* q = LP + DENSE_NZ * DENSE_NZ;
+    double pmax = 0.0;
+    for (int i = 0; i < DENSE_NZ; i++)
+        for (int j = 0; j < DENSE_NZ; j++) {
+            const bool in = i < r.nz && j < r.nz;
+            P[i * DENSE_NZ + j] = in ? r.P(i, j) : (i == j ? 1.0 : 0.0);
+            LP[i * DENSE_NZ + j] = (in && r.pd) ? (j <= i ? r.LP(i, j) : 0.0) : (i == j ? 1.0 : 0.0);
+            if (in) pmax = std::max(pmax, std::fabs(r.P(i, j)));
+        }
+    for (int i = 0; i < r.nz; i++) q[i] = r.q[i];
+    q[DENSE_NZ] = r.pd ? 0.0 : 1e-10 * std::max(1.0, pmax);  // the Newton ridge
+    for (int k = 0; k < b.m; k++) {
+        double* row = &b.dbl[DQ_HDR + (size_t)k * DQ_ROW];
+        for (int j = 0; j < r.nz; j++) row[j] = r.G(k, j);
+        row[DENSE_NZ] = r.lo[k];
+        row[DENSE_NZ + 1] = r.hi[k];
+    }
+    return b;
 }
 
 }  // namespace mpccbf

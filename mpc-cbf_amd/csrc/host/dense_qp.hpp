@@ -11,6 +11,7 @@
 // Rows whose reduced coefficients vanish are decided here (they only test the feasibility of xp).
 #pragma once
 
+#include <cstdint>
 #include <vector>
 
 #include "../../../include/mpccbf.h"
@@ -41,5 +42,16 @@ ReducedQP reduce_dense_qp(const mpccbf_dense_qp& qp);
 
 // x = xp + Z y; full-space objective x^T Hs x + c^T x + c0.
 void expand_solution(const ReducedQP& r, const double* y, double* x, double* obj);
+
+// A host-reduced QP as the device kernels read one (dense_qp.hip DenseBatch red / status / m / pd):
+// dbl = header [P | LP (both DENSE_NZ x DENSE_NZ, padded with the identity) | q | the Newton ridge
+// (0 when P is positive definite) | pad], then min(m, DENSE_ROWS) rows [g | lo | hi]; status = the
+// reduction's decision in dense_reduce_kernel's order (inconsistent equalities, capacity nz,
+// capacity rows, a violated constant row; else RS_SOLVE). A decided QP's doubles are zero.
+struct ReducedBlock {
+    std::vector<double> dbl;
+    int32_t status = 0, m = 0, pd = 0;
+};
+ReducedBlock device_block(const ReducedQP& r);
 
 }  // namespace mpccbf

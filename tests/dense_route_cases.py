@@ -1,7 +1,7 @@
 """Inputs of test_gpu_dense_routes.py (pinned on the CPU by test_dense_route_inputs.py): seeded
 dense QPs built so that the calls between them take every launch route of
 mpccbf_qp_solve_dense_batch, and predicted_route(), a restatement in Python of the rules by which
-the host chooses that route (dense_qp.hip, the body of mpccbf_qp_solve_dense_batch):
+the host chooses that route (csrc/host/dense_route.hpp, which dense_qp.hip follows):
 
   slices      4 pack / reduce slices when count >= 1024, else 1; each slice's reduce launch is sized
               by its own largest QP (LDS image rows and stride) and stages the packed QPs in LDS when
@@ -25,7 +25,7 @@ import numpy as np
 
 from test_dense_qp import INF, _random_qp
 
-# the host's constants (test_dense_route_inputs.py checks them against the source text)
+# the host's constants (test_dense_route_inputs.py checks them against the limits dense_route_check prints)
 WR = 3
 WROWS = 64 * WR
 DENSE_ROWS = 256
@@ -73,6 +73,38 @@ def plan(q):
     return dict(n=n, me=me, mi=mi, nh=nh, nd=nd, ni=ni, cap=cap)
 
 
+def route_of_shapes(shapes):
+    """The route of a call from its QPs' shapes alone (dicts with n, me, mi, nd, ni, cap, as plan()
+    gives them; mi: the rows the route counts): predicted_route's dict, and under slice_lds, per
+    slice, (dynamic LDS bytes, staged doubles, staged ints) of its reduce launch."""
+    count = len(shapes)
+    nslice = 4 if count >= SLICE_COUNT else 1
+    step = (count + nslice - 1) // nslice
+    rows_max = 1
+    slices, slice_lds = [], []
+    for q0 in range(0, count, step):
+        q1 = min(count, q0 + step)
+        nmax = emax = 1
+        sd = si = 0
+        for p in shapes[q0:q1]:
+            if p["cap"]:
+                continue
+            nmax, emax = max(nmax, p["n"]), max(emax, p["me"])
+            sd, si = max(sd, p["nd"] + 1), max(si, p["ni"] + 1)
+        stride = max(nmax, emax) | 1
+        lds = (nmax + ET_PAD) * stride * 8
+        staged = lds + sd * 8 + si * 4 <= STAGE_BYTES
+        slices.append((q0, q1, nmax, stride, staged))
+        slice_lds.append((lds + sd * 8 + si * 4, sd, si) if staged else (lds, 0, 0))
+    for p in shapes:
+        rows_max = max(rows_max, min(p["mi"], DENSE_ROWS))
+    big = [k for k, p in enumerate(shapes) if p["cap"]]
+    das = rows_max <= WROWS
+    return dict(slices=slices, slice_lds=slice_lds, rows_max=rows_max, active_set=das,
+                R=1 if rows_max <= 64 else (2 if rows_max <= 128 else DENSE_ROWS // 64),
+                early_exit=das and count <= EARLY_COUNT and not big, host_reduced=big)
+
+
 def predicted_route(qps):
     """The route one mpccbf_qp_solve_dense_batch call on qps takes: dict with
     slices      [(q0, q1, lds_rows, lds_stride, staged)] per pack / reduce slice,
@@ -82,31 +114,7 @@ def predicted_route(qps):
     R           the PDIP instantiation's row slots per lane,
     early_exit  whether the early exit after the active-set launch is possible,
     host_reduced  indices of the QPs reduced on the host."""
-    count = len(qps)
-    plans = [plan(q) for q in qps]
-    nslice = 4 if count >= SLICE_COUNT else 1
-    step = (count + nslice - 1) // nslice
-    rows_max = 1
-    slices = []
-    for q0 in range(0, count, step):
-        q1 = min(count, q0 + step)
-        nmax = emax = 1
-        sd = si = 0
-        for p in plans[q0:q1]:
-            if p["cap"]:
-                continue
-            nmax, emax = max(nmax, p["n"]), max(emax, p["me"])
-            sd, si = max(sd, p["nd"] + 1), max(si, p["ni"] + 1)
-        stride = max(nmax, emax) | 1
-        lds = (nmax + ET_PAD) * stride * 8
-        slices.append((q0, q1, nmax, stride, lds + sd * 8 + si * 4 <= STAGE_BYTES))
-    for p in plans:
-        rows_max = max(rows_max, min(p["mi"], DENSE_ROWS))
-    big = [k for k, p in enumerate(plans) if p["cap"]]
-    das = rows_max <= WROWS
-    return dict(slices=slices, rows_max=rows_max, active_set=das,
-                R=1 if rows_max <= 64 else (2 if rows_max <= 128 else DENSE_ROWS // 64),
-                early_exit=das and count <= EARLY_COUNT and not big, host_reduced=big)
+    return route_of_shapes([plan(q) for q in qps])
 
 
 # ------------------------------------------------------------------------------------------------

@@ -2,9 +2,11 @@
 that every QP has the status and the property its GPU test relies on (reduced dimension, active
 rows at the optimum, constant rows in the equalities' row space), and, for predicted_route (the
 restatement of the host's launch rules in dense_route_cases.py), that the calls between them take
-every route and that the rules' constants are still those of the source text."""
+every route and that the rules are the host's own: predicted_route against the route that
+tools/dense_route_check.cpp prints from csrc/host/dense_route.hpp, field by field."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +15,7 @@ import dense_route_cases as C
 import oracle_lib as O
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(REPO, "mpc-cbf_amd", "build", "dense_route_check")
 KKT = 1e-9
 
 
@@ -178,11 +181,16 @@ def test_group5_failing_calls():
     assert [k for k, q in enumerate(f["capacity"]) if C.plan(q)["mi"] > 256] == [C.CAP_AT]
 
 
-def test_every_route_is_taken():
-    """Every route the host can choose is taken by at least one call of the GPU tests."""
+def _gpu_test_calls():
     calls = [[q for _, q in C.group1()]] + [[C.row_edge_qp(mi)] for mi in C.ROW_EDGES]
     calls += [[C.constant_rows()["with_const"]], [C.zero_rows()["dropped"]]]
     calls += [v[0] for v in C.route_calls().values()] + [[q] for q in C.degenerate().values()]
+    return calls
+
+
+def test_every_route_is_taken():
+    """Every route the host can choose is taken by at least one call of the GPU tests."""
+    calls = _gpu_test_calls()
     routes = [C.predicted_route(c) for c in calls]
     assert {(r["R"], r["active_set"]) for r in routes} == {(1, True), (2, True), (4, True), (4, False)}
     assert {len(r["slices"]) for r in routes} == {1, 4}
@@ -193,35 +201,101 @@ def test_every_route_is_taken():
     assert any(r["active_set"] and r["host_reduced"] for r in routes)
 
 
-def test_predicted_route_constants_match_the_source():
-    """predicted_route restates rules of dense_qp.hip: when one of them changes there, this fails,
-    and the cases of dense_route_cases.py have to follow (or routes go untested)."""
-    csrc = os.path.join(REPO, "mpc-cbf_amd", "csrc")
-    src = open(os.path.join(csrc, "dense_qp.hip")).read()
-    wave = open(os.path.join(csrc, "kernels", "pdip_wave.hpp")).read()
+def _program(text=""):
+    if not os.path.exists(EXE):
+        pytest.fail(f"{EXE} not built (make -C mpc-cbf_amd)")
+    r = subprocess.run([EXE], input=text, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "FAIL" not in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    return r.stdout.strip().splitlines()
 
-    def num(text, pattern):
-        m = re.search(pattern, text)
-        assert m, pattern
-        return int(m.group(1))
 
-    assert num(wave, r"constexpr int WR = (\d+);") == C.WR
-    assert re.search(r"constexpr int WROWS = 64 \* WR;", wave)
-    assert num(src, r"constexpr int DENSE_ROWS = (\d+);") == C.DENSE_ROWS
-    assert num(src, r"constexpr int DENSE_NZ = (\d+);") == C.DENSE_NZ
-    assert num(src, r"constexpr int DENSE_NMAX = (\d+);") == C.DENSE_NMAX
-    assert num(src, r"constexpr int DENSE_EMAX = (\d+);") == C.DENSE_EMAX
-    assert num(src, r"constexpr int ET_PAD = (\d+);") == C.ET_PAD
-    m = re.search(r"nslice = count >= (\d+) \? (\d+) : (\d+);", src)
-    assert m and [int(v) for v in m.groups()] == [C.SLICE_COUNT, 4, 1]
-    assert num(src, r"e == hipSuccess && count <= (\d+) && big\.empty\(\)") == C.EARLY_COUNT
-    m = re.search(r"lds \+ stage <= (\d+) \* (\d+)", src)
-    assert m and int(m.group(1)) * int(m.group(2)) == C.STAGE_BYTES
-    assert re.search(r"a\.das_steps > 0 && rows_max <= dev::WROWS", src)
-    assert num(src, r"if \(rows_max <= (\d+)\) hipLaunchKernelGGL\(\(dev::dense_qp_kernel<DENSE_NZ, 1>\)") == 64
-    assert num(src, r"else if \(rows_max <= (\d+)\) hipLaunchKernelGGL\(\(dev::dense_qp_kernel<DENSE_NZ, 2>\)") == 128
-    assert re.search(r"else hipLaunchKernelGGL\(\(dev::dense_qp_kernel<DENSE_NZ, DQ_R>\)", src)
-    assert re.search(r"rows_max = std::max\(rows_max, std::min\(plan\[k\]\.mi, DENSE_ROWS\)\);", src)
+def _program_routes(calls):
+    """dense_route_check on lists of shapes: (its limits, one route per call in predicted_route's form)."""
+    text = "".join(f"{len(c)}\n" + "".join(f"{p['n']} {p['me']} {p['mi']} {p['nd']} {p['ni']} {int(p['cap'])}\n"
+                                           for p in c) for c in calls)
+    lines = _program(text)
+    assert lines[0].startswith("limits ") and len(lines) == 1 + len(calls), lines[:2]
+    limits = {k: int(v) for k, v in (f.split("=") for f in lines[0].split()[1:])}
+    routes = []
+    for ln in lines[1:]:
+        f = dict(t.split("=") for t in ln.split()[1:])
+        sl = [tuple(int(v) for v in s.split(":")) for s in f["slices"].split(";")]
+        routes.append(dict(slices=[s[:4] for s in sl], slice_lds=[s[4:] for s in sl], rows_max=int(f["rows_max"]),
+                           active_set=bool(int(f["active_set"])), R=int(f["R"]), early_exit=bool(int(f["early_exit"])),
+                           host_reduced=[int(v) for v in f["host_reduced"].split(",") if v]))
+    return limits, routes
+
+
+def _shape(n=12, me=5, mi=10, nd=300, ni=60, cap=False):
+    return dict(n=n, me=me, mi=mi, nd=nd, ni=ni, cap=cap)
+
+
+def _edge_calls():
+    """name -> shapes: a call at every edge of the route's rules (no QP behind them)."""
+    calls = {f"count {c}": [_shape()] * c for c in (1, 64, 65, 1023, 1024, 1027)}
+    calls.update({f"rows {m}": [_shape(mi=m)] for m in (64, 65, 128, 129, 192, 193, 256, 300)})
+    # image (40 + 8) x 41 doubles = 15744 bytes; 4126 doubles + 100 ints staged: 49152 bytes in all
+    calls["48 KB"] = [_shape(n=40, me=10, nd=4125, ni=99)]
+    calls["48 KB + an int"] = [_shape(n=40, me=10, nd=4125, ni=100)]
+    calls["48 KB + a double"] = [_shape(n=40, me=10, nd=4126, ni=99)]
+    calls["n 64, me 1"] = [_shape(n=64, me=1)]
+    calls["n 1, me 64"] = [_shape(n=1, me=64)]
+    cap = _shape(n=80, me=70, mi=40, nd=0, ni=0, cap=True)
+    calls["cap alone"] = [cap]
+    calls["cap first in a slice"] = [_shape()] * 257 + [cap] + [_shape()] * 769
+    calls["cap last in a call"] = [_shape()] * 1026 + [cap]
+    calls["cap in a small call"] = [_shape()] * 15 + [cap]
+    calls["only the host-reduced QP beyond 192 rows"] = [_shape(mi=192), dict(cap, mi=193)]
+    calls["only the host-reduced QP beyond 128 rows"] = [_shape(mi=64), dict(cap, mi=129)]
+    return calls
+
+
+def test_predicted_route_is_the_programs_route():
+    """predicted_route restates csrc/host/dense_route.hpp, which mpccbf_qp_solve_dense_batch follows:
+    field by field against tools/dense_route_check.cpp (the header's own functions), for every call of
+    the GPU tests and at every edge of the rules; the constants kept on the Python side against the
+    limits the program prints."""
+    calls = {f"gpu call {k}": [C.plan(q) for q in c] for k, c in enumerate(_gpu_test_calls())}
+    calls.update(_edge_calls())
+    limits, got = _program_routes(list(calls.values()))
+    assert limits == dict(DENSE_NZ=C.DENSE_NZ, DENSE_ROWS=C.DENSE_ROWS, DENSE_NMAX=C.DENSE_NMAX,
+                          DENSE_EMAX=C.DENSE_EMAX, ET_PAD=C.ET_PAD, DAS_ROWS=64 * C.WR, SLICE_COUNT=C.SLICE_COUNT,
+                          MAX_SLICES=4, EARLY_COUNT=C.EARLY_COUNT, STAGE_BYTES=C.STAGE_BYTES, PACK_SPARE=1)
+    assert C.WROWS == 64 * C.WR
+    want = {}
+    for (name, shapes), g in zip(calls.items(), got):
+        w = want[name] = C.route_of_shapes(shapes)
+        assert [s[:4] for s in w["slices"]] == g["slices"], name
+        assert w["slice_lds"] == g["slice_lds"], name
+        for key in ("rows_max", "active_set", "R", "early_exit", "host_reduced"):
+            assert w[key] == g[key], (name, key, w[key], g[key])
+    # the edges are edges: both sides of every comparison are among the calls
+    assert [len(want[f"count {c}"]["slices"]) for c in (1023, 1024, 1027)] == [1, 4, 4]
+    assert [want[f"count {c}"]["early_exit"] for c in (1, 64, 65)] == [True, True, False]
+    assert [(want[f"rows {m}"]["R"], want[f"rows {m}"]["active_set"]) for m in (64, 65, 128, 129, 192, 193, 256, 300)] \
+        == [(1, True), (2, True), (2, True), (4, True), (4, True), (4, False), (4, False), (4, False)]
+    assert want["rows 300"]["rows_max"] == 256
+    assert want["48 KB"]["slice_lds"] == [(C.STAGE_BYTES, 4126, 100)]
+    assert want["48 KB + an int"]["slice_lds"] == want["48 KB + a double"]["slice_lds"] == [(15744, 0, 0)]
+    assert want["n 64, me 1"]["slices"] == [(0, 1, 64, 65, True)] and want["n 1, me 64"]["slices"] == [(0, 1, 1, 65, True)]
+    assert want["cap alone"]["slices"] == [(0, 1, 1, 1, True)] and want["cap alone"]["slice_lds"] == [(72, 0, 0)]
+    assert want["cap alone"]["host_reduced"] == [0] and not want["cap alone"]["early_exit"]
+    assert want["cap first in a slice"]["host_reduced"] == [257] and want["cap first in a slice"]["slices"][1][:2] == (257, 514)
+    assert want["cap last in a call"]["host_reduced"] == [1026]
+    assert want["cap in a small call"]["active_set"] and not want["cap in a small call"]["early_exit"]
+    w = want["only the host-reduced QP beyond 192 rows"]
+    assert (w["rows_max"], w["active_set"], w["R"]) == (193, False, 4)
+    w = want["only the host-reduced QP beyond 128 rows"]
+    assert (w["rows_max"], w["active_set"], w["R"]) == (129, True, 4)
+
+
+def test_dense_route_check_checks_itself():
+    """Without input the program checks the three buffers' layout (alignment, disjoint sections inside
+    the reserved totals), the slices, the slot bounds against plan_qp's exact sizes and the
+    host-reduced block by position."""
+    last = _program()[-1]
+    m = re.fullmatch(r"dense_route_check: (\d+) checks, 0 failures", last)
+    assert m and int(m.group(1)) > 50000, last
 
 
 @pytest.mark.parametrize("shape", [(6, 2, 5, 0, 0), (12, 5, 20, 0, 1), (20, 14, 0, 0, 3), (40, 33, 40, 2, 2)])

@@ -195,3 +195,38 @@ def test_call_sequence_on_one_thread(mpclib, oracle):
         _compare(mpclib, big1, k, q, where="large, first")
     assert _identical_calls(small1, small2)
     assert _identical_calls(big1, big2)
+
+
+def test_fresh_thread_grows_every_buffer_from_nothing(mpclib, route_results):
+    """The pinned input, the pinned output and the device block are kept per thread: on a fresh
+    thread all three are empty, so the sequence one QP (n = 1, no rows: every section at its
+    smallest), call d (65 QPs), call e (1027 QPs, 4 slices, one host-reduced), one QP again lays
+    every section out at its smallest, grows each buffer twice and reuses it. The one-QP call
+    against its closed form x = -c / (2 h), obj = -c^2 / (4 h) (this file's tolerances: x 1e-5,
+    objective 1e-6); every call bit for bit what the main thread's call returned."""
+    import threading
+    calls = C.route_calls()
+    h, c = 2.5, -3.0
+    one = [dict(H=np.array([[h]]), c=np.array([c]))]
+    order = (one, calls["d"][0], calls["e"][0], one)
+    main_one = mpclib.dense_qp_solve_batch(one)
+    got, err = [], []
+
+    def worker():
+        try:
+            for qps in order:
+                got.append(mpclib.dense_qp_solve_batch(qps))
+        except BaseException as ex:  # (reported on the main thread)
+            err.append(ex)
+
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert not err, err
+    assert len(got) == 4
+    for r in (main_one, got[0], got[3]):
+        assert r[0][0] == mpclib.OPTIMAL
+        assert abs(r[1][0][0] + c / (2.0 * h)) <= 1e-5 and abs(r[2][0] + c * c / (4.0 * h)) <= 1e-6
+    assert _identical_calls(got[0], main_one) and _identical_calls(got[3], main_one)
+    assert _identical_calls(got[1], route_results["d"])
+    assert _identical_calls(got[2], route_results["e"])

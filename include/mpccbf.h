@@ -624,6 +624,64 @@ typedef struct mpccbf_pf_batch {
 int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* hip_stream);
 int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* hip_stream);
 
+/* ---- FoV IMPC on each observer's own neighbour estimates (feature macro; MPCCBF_ABI_VERSION is
+ * unchanged: no struct changed layout) -----------------------------------------------------------
+ *
+ * FovBezierIMPCCBF::optimize(curves, state, other_robot_positions, other_robot_covs, ref) plans from
+ * one position and one covariance per (observer, neighbour) pair (FovBezierIMPCCBF.cpp:48-52); both
+ * feed the Voronoi rows, the four FoV CBF rows of every IMPC iteration and the distanceToEllipse
+ * slack order (:58-81, 115-200). mpccbf_set_fov_estimates attaches those two vectors to a context of
+ * the FoV controller (the attach idiom of mpccbf_set_active_store / mpccbf_set_connectivity).
+ *
+ * Pair indexing: pair e is CSR entry e of the batch's nb_row_ptr / nb_col, and e indexes every
+ * per-pair buffer — mpccbf_pf_batch's indexing, a nonzero nb_row_ptr[0] included: est_xy / est_cov of
+ * mpccbf_pf_step pass unchanged as nb_xy / nb_cov.
+ *
+ * While attached, every FoV mpccbf_impc_solve / mpccbf_run_steps step (CSR lists) changes two reads:
+ *   - pair e's neighbour position is nb_xy[e] where it was states[nb_col[e]]: in the Voronoi rows, in
+ *     the safety / left / right / range rows of iteration 0 and in their predicted forms of the later
+ *     iterations;
+ *   - the slack order is by distanceToEllipse(ego, nb_xy[e], nb_cov[e]), or -5 for every pair when
+ *     nb_cov is NULL (the list order applies); mpccbf_batch::cov is ignored.
+ * nb_col[e] still names the neighbour: it is what nb_out reports and the row the filter measures.
+ * Nothing else changes: the ego state, targets, closed-loop store, noise and outputs are as they are.
+ * mpccbf_kernel_name reports the estimate form, impc_fov_kernel<false,true> / <true,true>.
+ *
+ * With pf given, est_xy / est_cov must be the buffers nb_xy / nb_cov name (nb_cov may be NULL), and
+ * step s of mpccbf_run_steps enqueues mpccbf_pf_step over the batch's lists against the table that
+ * step reads, with step_index = batch.step_index + s and input NULL, ahead of the step's IMPC launch
+ * on the same stream: mpccbf_run_steps(n) is bit for bit n x (mpccbf_pf_step; mpccbf_impc_solve).
+ * mpccbf_impc_solve never steps the filter; the caller runs mpccbf_pf_init itself. pf is copied; the
+ * buffers stay the caller's and must outlive the attach.
+ *
+ * Refused at the attach with MPCCBF_ERR_INVALID_ARGUMENT, on the host before any device call: the
+ * collision controller (cbf_mode 0), num_pairs < 0, a NULL nb_xy with num_pairs > 0, pf with a
+ * missing buffer (particles, weights, est_xy, est_cov), with est_xy != nb_xy, with a nb_cov that is
+ * neither NULL nor est_cov, or with parameters mpccbf_pf_step refuses. Refused at a solve with
+ * MPCCBF_ERR_INVALID_ARGUMENT while attached: grid mode (nb_row_ptr NULL: estimates belong to fixed
+ * pairs) and a communicator of more than one rank.
+ *
+ * On the device: an observer whose list reaches a pair index >= num_pairs reports MPCCBF_ERROR for
+ * its QPs and reads nothing out of range; an observer with a non-finite estimate reports MPCCBF_ERROR
+ * (the non-finite rule of every solve); every other agent is unaffected in both cases. The
+ * per-observer caps are those of the unattached solve (16 observed neighbours, 8 in slack mode).
+ * After a detach every call is what it was before the attach. */
+#define MPCCBF_HAS_FOV_ESTIMATES 1
+typedef struct mpccbf_fov_estimates {
+    int32_t num_pairs;        /* rows of every per-pair buffer */
+    const double* nb_xy;      /* device, pairs x 2: est_xy's format */
+    const double* nb_cov;     /* device, pairs x 3 (cxx, cxy, cyy), or NULL = unknown (infinite) */
+    /* optional filter driven by mpccbf_run_steps (pf NULL: the estimates are the caller's and the
+     * buffers below are not read) */
+    const mpccbf_pf_params* pf;   /* copied */
+    double* particles;        /* pairs x 2 x P */
+    double* weights;          /* pairs x P */
+    double* est_xy;           /* == nb_xy */
+    double* est_cov;          /* == nb_cov unless that is NULL */
+    int32_t* flags;           /* pairs, or NULL */
+} mpccbf_fov_estimates;
+int mpccbf_set_fov_estimates(mpccbf_ctx* ctx, const mpccbf_fov_estimates* e /* NULL detaches */);
+
 /* ---- Batched CBF-only connectivity controller (ConnectivityControl::optimize,
  * cbf/src/controller/ConnectivityControl.cpp:22-99) for teams of robots ----------------------
  * Per robot of a team (<= 16 robots; robots of team t are rows team_ptr[t] .. team_ptr[t+1]-1):
@@ -740,7 +798,9 @@ int mpccbf_host_launch_plan(const mpccbf_params* p, const mpccbf_options* opt, i
 enum {
     MPCCBF_FACT_TARGETS = 0, MPCCBF_FACT_TRAJ_T, MPCCBF_FACT_SUBSTEPS, MPCCBF_FACT_COV, MPCCBF_FACT_NB_OUT,
     MPCCBF_FACT_PRIMAL_RES, MPCCBF_FACT_DUAL_RES, MPCCBF_FACT_CONE, MPCCBF_FACT_X, MPCCBF_FACT_STATUS,
-    MPCCBF_FACT_OBJ, MPCCBF_FACT_ITERS, MPCCBF_FACT_NEXT_STATES, MPCCBF_FACT_INSERT, MPCCBF_FACT_COUNT
+    MPCCBF_FACT_OBJ, MPCCBF_FACT_ITERS, MPCCBF_FACT_NEXT_STATES, MPCCBF_FACT_INSERT,
+    MPCCBF_FACT_EST, /* per-pair FoV estimates attached (mpccbf_set_fov_estimates) */
+    MPCCBF_FACT_COUNT
 };
 int mpccbf_host_launch_form(const mpccbf_params* p, const mpccbf_options* opt, int32_t variant,
                             int32_t num_agents, int32_t csr, int32_t knn_k, int32_t store,

@@ -18,6 +18,7 @@
 
 #include "../../include/mpccbf.h"
 #include "host/defer_queues.hpp"
+#include "host/fov_estimates.hpp"
 #include "host/grid_rotation.hpp"
 #include "host/hip_host.hpp"
 #include "host/operators.hpp"
@@ -26,6 +27,7 @@
 #include "kernels/cap_audit.hpp"
 #include "kernels/conn_rows.hpp"
 #include "kernels/launch_plan.hpp"
+#include "kernels/pf_fov.hpp"
 
 namespace mpccbf {
 
@@ -113,13 +115,22 @@ struct mpccbf_ctx {
         mpccbf::DevBuf d_team_ptr, d_team_mode, d_row_team;  // int32
         mpccbf::DevBuf d_team_l2, d_fiedler;                 // double
     } conn;
+    // per-pair neighbour estimates (mpccbf_set_fov_estimates): the caller's buffers as attached
+    // (e.pf: null, or &pf, the copied filter parameters mpccbf_run_steps steps the filter with)
+    struct {
+        bool on = false;
+        mpccbf_fov_estimates e{};
+        mpccbf_pf_params pf{};
+    } est;
 };
 
 using namespace mpccbf;
 
 // The launch plan of the context's next IMPC step for n agents (launch_plan.hpp)
 static LaunchPlan ctx_plan(const mpccbf_ctx* c, int n, bool csr, int knn_k, bool store) {
-    return impc_launch_plan(c->dev, c->variant, n, csr, knn_k, store, c->conn.on);
+    LaunchFacts f{};
+    f.est = c->est.on;
+    return impc_launch_plan(c->dev, c->variant, n, csr, knn_k, store, c->conn.on, f);
 }
 
 // Warm-start threshold when mpccbf_set_active_store is given min_steps = 0
@@ -177,6 +188,8 @@ static int check_batch(const mpccbf_ctx* c, const mpccbf_batch* b, bool grid, co
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "traj_t (closed-loop fallback) needs the persistent x buffer");
     if (!(b->pos_std >= 0.0) || !(b->vel_std >= 0.0))
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "noise standard deviations must be >= 0");
+    const std::string est_err = fov_estimates_solve_error(c->est.on, grid, 1);
+    if (!est_err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, est_err);
     if (store && c->store_rows < b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "active store: rows (" + std::to_string(c->store_rows) +
                                                      ") < num_states (" + std::to_string(b->num_states) + ")");
@@ -310,6 +323,14 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     if (conn && (rc = enqueue_spectrum(c, b, stream, cn)) != MPCCBF_OK) return rc;
     if (grid && (rc = grid_args(c, b, ops, roles, stream, a.grid)) != MPCCBF_OK) return rc;
     batch_args(b, kclock, a);
+    // (attached only to contexts of the FoV controller, whose launches alone read them)
+    if (c->est.on && ops.cbf_mode == 1) {
+        a.est_xy = c->est.e.nb_xy;
+        a.est_cov = c->est.e.nb_cov;
+        a.est_pairs = c->est.e.num_pairs;
+        // (no pair: no list can reach one; a non-null pointer keeps the estimate form, which reads nothing)
+        if (!a.est_xy) a.est_xy = b->states;
+    }
     // facts and plan
     const LaunchPlan plan = impc_launch_plan(ops, c->variant, b->num_agents, !grid, b->knn_k, store != nullptr, conn,
                                              launch_facts(a));
@@ -335,6 +356,8 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
         const int blocks = (ia.num_agents + per_block - 1) / per_block;
         if (k == IMPC_CONN) return launch_impc_conn(k, blocks, bs, ops, buf, ia, cn, stream);
         if (k == IMPC_FOV || k == IMPC_FOV_SLACK) return launch_impc_fov(k, blocks, bs, ops, buf, ia, stream);
+        if (k == IMPC_FOV_EST || k == IMPC_FOV_SLACK_EST)
+            return launch_impc_fov_est(k, blocks, bs, ops, buf, ia, stream);
         if (plan.store) return launch_impc_store(k, blocks, bs, ops, buf, ia, st, stream);
         return launch_impc(k, blocks, bs, ops, buf, ia, stream);
     };
@@ -499,6 +522,24 @@ int mpccbf_set_connectivity(mpccbf_ctx* c, const mpccbf_connectivity* k) {
     d.team_ptr.assign(k->team_ptr, k->team_ptr + k->num_teams + 1);
     d.out_l2 = k->lambda2;
     d.out_fiedler = k->fiedler;
+    return MPCCBF_OK;
+}
+
+int mpccbf_set_fov_estimates(mpccbf_ctx* c, const mpccbf_fov_estimates* e) {
+    if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null context");
+    if (!e) {
+        c->est.on = false;
+        c->est.e = mpccbf_fov_estimates{};
+        return MPCCBF_OK;
+    }
+    const std::string err = fov_estimates_attach_error(c->dev.cbf_mode, *e);
+    if (!err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, err);
+    c->est.on = true;
+    c->est.e = *e;
+    if (e->pf) {
+        c->est.pf = *e->pf;
+        c->est.e.pf = &c->est.pf;
+    }
     return MPCCBF_OK;
 }
 
@@ -761,6 +802,10 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
     if (first < 0 || count < 0 || first + count > ns) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent range outside states");
     if (r->comm && (ns != r->comm->nranks * count || first != r->comm->rank * count))
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: ranks must own equal contiguous agent blocks");
+    {
+        const std::string est_err = fov_estimates_solve_error(c->est.on, false, r->comm ? r->comm->nranks : 1);
+        if (!est_err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, est_err);
+    }
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     const bool timing = r->step_ms || r->solve_ms;
@@ -813,6 +858,28 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
             if (tail > 0)
                 HIP_TRY(hipMemcpyAsync(nxt + (size_t)(first + count) * 6, cur + (size_t)(first + count) * 6,
                                        (size_t)tail * 6 * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        }
+        // the attached filter's step against the table this step reads, ahead of the IMPC launch:
+        // mpccbf_pf_step over the batch's lists (pairs beyond the attached rows are skipped)
+        if (c->est.on && c->est.e.pf && b->nb_row_ptr && count > 0) {
+            const auto& e = c->est.e;
+            mpccbf_pf_batch pb;
+            std::memset(&pb, 0, sizeof(pb));
+            pb.num_states = ns;
+            pb.states = cur;
+            pb.agent_first = first;
+            pb.num_agents = count;
+            pb.nb_row_ptr = b->nb_row_ptr;
+            pb.nb_col = b->nb_col;
+            pb.num_pairs = e.num_pairs;  // (blocks; past the lists' end they leave at once)
+            pb.particles = e.particles;
+            pb.weights = e.weights;
+            pb.est_xy = e.est_xy;
+            pb.est_cov = e.est_cov;
+            pb.flags = e.flags;
+            pb.step_index = b->step_index + s;
+            const int prc = pf_enqueue(e.pf, &pb, c->device, stream, false, e.num_pairs);
+            if (prc != MPCCBF_OK) return prc;
         }
         const bool tk = r->solve_ms && (r->solve_stride <= 1 || s % r->solve_stride == 0);
         const int rc = impc_enqueue(c, &sb, stream, tk ? ev[3 * s + 1] : nullptr, tk ? ev[3 * s + 2] : nullptr,

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/mpccbf.h"
+#include "host/fov_estimates.hpp"
 #include "host/hip_host.hpp"
 #include "kernels/cbf_control.hpp"
 #include "kernels/launch_plan.hpp"
@@ -132,19 +133,19 @@ int mpccbf_fov_control_solve(const mpccbf_fov_control_params* p, const mpccbf_fo
     return MPCCBF_OK;
 }
 
-// mpccbf_pf_init / mpccbf_pf_step: every argument check runs on the host before any device call
-static int pf_call(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream,
-                   bool init) {
+static_assert(PF_PARTICLES_MIN == PF_MIN_PARTICLES && PF_PARTICLES_MAX == PF_MAX_PARTICLES,
+              "fov_estimates.hpp's particle bounds are the kernels'");
+
+}  // extern "C"
+
+// mpccbf_pf_init / mpccbf_pf_step: every argument check runs on the host before any device call.
+// pair_rows > 0 (the filter mpccbf_run_steps drives): rows of the per-pair buffers, pairs beyond
+// them are skipped.
+int mpccbf::pf_enqueue(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream, bool init,
+                       int32_t pair_rows) {
     if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    if (p->num_particles < PF_MIN_PARTICLES || p->num_particles > PF_MAX_PARTICLES)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_particles must be in 2 .. 1024");
-    auto pos_def = [](const double* c) {
-        return c[0] > 0.0 && c[0] * c[2] - c[1] * c[1] > 0.0 && std::isfinite(c[0]) && std::isfinite(c[1]) &&
-               std::isfinite(c[2]);
-    };
-    if (!pos_def(p->init_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "init_cov must be positive definite");
-    if (!pos_def(p->meas_cov)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "meas_cov must be positive definite");
-    if (!(p->weight_reduction > 0.0)) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "weight_reduction must be positive");
+    const std::string perr = pf_params_error(*p);
+    if (!perr.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, perr);
     if (b->num_states < 0 || b->num_agents < 0 || b->num_pairs < 0 || b->agent_first < 0)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "negative count");
     if ((int64_t)b->agent_first + b->num_agents > b->num_states)
@@ -192,16 +193,19 @@ static int pf_call(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t 
     a.fov = p->fov;
     a.Rs = p->Rs;
     a.weight_reduction = p->weight_reduction;
+    a.pair_rows = pair_rows;
     HIP_TRY(init ? launch_pf_init(a, (hipStream_t)stream) : launch_pf_step(a, (hipStream_t)stream));
     return MPCCBF_OK;
 }
 
+extern "C" {
+
 int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
-    return pf_call(p, b, device, stream, true);
+    return pf_enqueue(p, b, device, stream, true, 0);
 }
 
 int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
-    return pf_call(p, b, device, stream, false);
+    return pf_enqueue(p, b, device, stream, false, 0);
 }
 
 }  // extern "C"

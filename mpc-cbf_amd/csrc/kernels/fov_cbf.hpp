@@ -1,5 +1,5 @@
 // fov_cbf.hpp — closed form of the FoV HOCBF rows (FovCBF::init*CBF, FovCBF.cpp:152-535), shared by
-// the FoV MPC kernel (impc_fov.hip) and the batched CBF-only controller (cbf_control.hip).
+// the FoV MPC kernel (impc_fov.hpp) and the batched CBF-only controller (cbf_control.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -200,6 +200,14 @@ struct ImpcArgs {
     // launch clock (mpccbf_run::kernel_clock): per wave of the launch its (start, end)
     // s_memrealtime pair (100 MHz; impc_common.hpp kclock_*), or nullptr
     unsigned long long* kclock;
+    // FoV controller, estimate form (mpccbf_set_fov_estimates; CSR lists only): per pair e = CSR
+    // entry e of nb_col the observer's estimate of that neighbour's position, est_pairs x 2, and
+    // its covariance (cxx, cxy, cyy), est_pairs x 3 or nullptr (unknown). est_xy == nullptr: none
+    // attached (the neighbour's row of `states` and `cov`). At the end: the kernels that read
+    // neither keep every other field where it was.
+    const double* est_xy;
+    const double* est_cov;
+    int32_t est_pairs;
 };
 
 // active-set store (mpccbf_set_active_store), an argument of its own of the store kernels (not a

@@ -1,5 +1,5 @@
 // impc_common.hpp — device steps shared by the IMPC kernels (impc_dense.hpp, impc_sep.hpp,
-// impc_wide_kernels.hpp, impc_fov.hip):
+// impc_wide_kernels.hpp, impc_fov.hpp):
 // the collision HOCBF row, the in-kernel neighbour query, the state-dependent linear term, the
 // constant-row check, CBF-row staging, objective and output writes, diagnostics stamps.
 #pragma once

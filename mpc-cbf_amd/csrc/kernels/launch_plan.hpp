@@ -34,10 +34,12 @@ enum ImpcKernel : int32_t {
     IMPC_QUEUE1_STORE, //   impc_sep_store_kernel<1,64,true>
     IMPC_QUEUE8_STORE, //   impc_sep_store_kernel<8,64,true>
     IMPC_CONN,         // impc_conn.hip: impc_sep_conn_kernel<4,64> (impc_sep.hpp)
-    IMPC_FOV,          // impc_fov.hip: impc_fov_kernel<false>
+    IMPC_FOV,          // impc_fov.hip: impc_fov_kernel<false> (impc_fov.hpp)
     IMPC_FOV_SLACK,    //   impc_fov_kernel<true>
     IMPC_SEP_LOOP,     // impc_kernel.hip: IMPC_SEP in the loop form (FORM_LOOP, impc.hpp), reported under
                        //   IMPC_SEP's name
+    IMPC_FOV_EST,        // impc_fov_est.hip: impc_fov_kernel<false,true>, the estimate form (ImpcArgs::est_xy)
+    IMPC_FOV_SLACK_EST,  //   impc_fov_kernel<true,true>
 };
 
 // What is the same for every agent of one launch and known where ImpcArgs is filled (impc_enqueue):
@@ -49,6 +51,7 @@ struct LaunchFacts {
     bool cone;         // GridArgs::cone > 0
     bool x, status, obj, iters, next_states;  // outputs given
     bool insert;       // the launch fills the next step's neighbour table (GridArgs::ins_cnt)
+    bool est;          // per-pair neighbour estimates attached (ImpcArgs::est_xy; FoV controller)
 };
 
 // The facts of these arguments, as a launch with them holds them
@@ -68,6 +71,7 @@ inline LaunchFacts launch_facts(const ImpcArgs& a) {
     f.iters = a.iters != nullptr;
     f.next_states = a.next_states != nullptr;
     f.insert = a.grid.ins_cnt != nullptr;
+    f.est = a.est_xy != nullptr;
     return f;
 }
 
@@ -95,7 +99,8 @@ extern const int IMPC_FOV_ROWS_MAX;
 // Pure: no HIP runtime call, no context state. `op` as mpccbf_create packed it (a store attached
 // turns DevOps::lean off here, not in a copy); n: the agents of the launch.
 // facts: the launch-uniform options; IMPC_SEP becomes IMPC_SEP_LOOP (same name, shape and clock)
-// exactly when every one of them is what the loop form fixes.
+// exactly when every one of them is what the loop form fixes; IMPC_FOV / IMPC_FOV_SLACK become
+// their estimate forms exactly when facts.est is set.
 LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int knn_k, bool store, bool conn,
                             const LaunchFacts& facts = LaunchFacts{});
 
@@ -118,6 +123,8 @@ hipError_t launch_impc_conn(ImpcKernel k, int blocks, int block_size, const DevO
                             const ImpcArgs& a, const ConnArgs& cn, hipStream_t s);
 hipError_t launch_impc_fov(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
                            const ImpcArgs& a, hipStream_t s);
+hipError_t launch_impc_fov_est(ImpcKernel k, int blocks, int block_size, const DevOps& op, const double* buf,
+                               const ImpcArgs& a, hipStream_t s);
 
 // The library's other launches (impc_fov.hip, impc_conn.hip, cap_audit.hip, neighbors.hip)
 hipError_t launch_fov_rows_eval(int count, const double* ego, const double* nb, double fov, double Ds, double Rs,

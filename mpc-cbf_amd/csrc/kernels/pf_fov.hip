@@ -34,11 +34,11 @@ __device__ __forceinline__ double pf_wave_sum(double v) {
 }
 
 // The pair of this block: CSR entry e, its observer's and its neighbour's rows of the state table.
-// False (for the whole block) when the block is past the last pair or the neighbour index is not a
-// row of the table.
+// False (for the whole block) when the block is past the last pair (of the lists, or of the buffers
+// where pair_rows gives their rows) or the neighbour index is not a row of the table.
 __device__ __forceinline__ bool pf_locate(const PfArgs& a, int& e, int& obs, int& nb) {
     e = a.nb_row_ptr[0] + (int)blockIdx.x;
-    if (e >= a.nb_row_ptr[a.num_agents]) return false;
+    if (e >= a.nb_row_ptr[a.num_agents] || (a.pair_rows > 0 && e >= a.pair_rows)) return false;
     int lo = 0, hi = a.num_agents;  // nb_row_ptr[lo] <= e < nb_row_ptr[hi]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;

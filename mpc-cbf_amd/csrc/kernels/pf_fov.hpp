@@ -5,6 +5,9 @@
 
 #include <cstdint>
 
+struct mpccbf_pf_params;
+struct mpccbf_pf_batch;
+
 namespace mpccbf {
 
 constexpr int PF_MIN_PARTICLES = 2;
@@ -33,9 +36,14 @@ struct PfArgs {
     double process[4];          // W, row-major (a plain multiplier: particle_filter.cpp:73)
     double meas_inv[3];         // R^-1 (ixx, ixy, iyy)
     double dt, fov, Rs, weight_reduction;
+    int32_t pair_rows;          // > 0: rows of the per-pair buffers, a pair e >= pair_rows is skipped
 };
 
 hipError_t launch_pf_init(const PfArgs& a, hipStream_t s);
 hipError_t launch_pf_step(const PfArgs& a, hipStream_t s);
+
+// The body of mpccbf_pf_init / mpccbf_pf_step (capi_control.hip): checks, arguments, one launch
+int pf_enqueue(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream, bool init,
+               int32_t pair_rows);
 
 }  // namespace mpccbf

@@ -47,8 +47,10 @@ const KernelShape SHAPES[] = {
     {"impc_fov_kernel<false>", 64, 1, false},
     {"impc_fov_kernel<true>", 64, 1, false},
     {"impc_sep_kernel<1,1,false,256>", 256, 16, true},  // (the loop form: IMPC_SEP's name)
+    {"impc_fov_kernel<false,true>", 64, 1, false},
+    {"impc_fov_kernel<true,true>", 64, 1, false},
 };
-static_assert(sizeof(SHAPES) / sizeof(SHAPES[0]) == IMPC_SEP_LOOP + 1, "one shape per ImpcKernel");
+static_assert(sizeof(SHAPES) / sizeof(SHAPES[0]) == IMPC_FOV_SLACK_EST + 1, "one shape per ImpcKernel");
 
 constexpr int VARIANT_SEP16 = 4, VARIANT_WIDE = 5;
 
@@ -74,6 +76,7 @@ static LaunchFacts launch_facts_of_bits(uint32_t bits) {
     f.iters = on(MPCCBF_FACT_ITERS);
     f.next_states = on(MPCCBF_FACT_NEXT_STATES);
     f.insert = on(MPCCBF_FACT_INSERT);
+    f.est = on(MPCCBF_FACT_EST);
     return f;
 }
 
@@ -105,7 +108,7 @@ LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int 
     const bool dense16 = op.m < 64 && (variant == 3 || (variant == 0 && !csr && knn_k * op.cbf_h <= 64 - op.m));
 
     // the loop form (FORM_LOOP, impc.hpp): every launch-uniform option as that form fixes it
-    const bool loop = !csr && f.targets && f.traj_t && !f.substeps && !f.cov && !f.cone && !f.nb_out &&
+    const bool loop = !csr && f.targets && f.traj_t && !f.substeps && !f.cov && !f.cone && !f.nb_out && !f.est &&
                       !f.primal_res && !f.dual_res && f.x && f.status && f.obj && f.iters && f.next_states && f.insert;
 
     LaunchPlan p{};
@@ -117,8 +120,10 @@ LaunchPlan impc_launch_plan(const DevOps& op, int variant, int n, bool csr, int 
     } else if (op.cbf_mode == 1) {
         // (slack mode: 4 kinds x cbf_h rows per 8-lane segment)
         const bool ok = op.nz == 15 && op.m <= IMPC_FOV_ROWS_MAX && (!slack || op.cbf_h <= 2);
-        p.kernel = !ok ? IMPC_NONE : (slack ? IMPC_FOV_SLACK : IMPC_FOV);
-        p.name = SHAPES[slack ? IMPC_FOV_SLACK : IMPC_FOV].name;
+        // (the estimate form: the same kernel reading the per-pair buffers, mpccbf_set_fov_estimates)
+        const ImpcKernel k = f.est ? (slack ? IMPC_FOV_SLACK_EST : IMPC_FOV_EST) : (slack ? IMPC_FOV_SLACK : IMPC_FOV);
+        p.kernel = !ok ? IMPC_NONE : k;
+        p.name = SHAPES[k].name;
     } else {
         p.store = store && !slack && (wide || full16);
         if (slack) {

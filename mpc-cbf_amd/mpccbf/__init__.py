@@ -14,3 +14,4 @@ from ._lib import (  # noqa: F401
 from . import swarm  # noqa: F401
 from .estimator import FovEstimator  # noqa: F401
 from .fov_control_sim import FovControlLoop  # noqa: F401
+from .fov_impc_sim import FovImpcLoop  # noqa: F401

@@ -25,7 +25,7 @@ EXPORTED = [
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
     "mpccbf_set_active_store", "mpccbf_cap_audit_run", "mpccbf_set_connectivity",
     "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step", "mpccbf_launch_form",
-    "mpccbf_host_launch_form",
+    "mpccbf_host_launch_form", "mpccbf_set_fov_estimates",
 ]
 
 # ImpcKernel ids (csrc/kernels/launch_plan.hpp) of the 16-lane main launch: generic and loop form
@@ -33,7 +33,7 @@ IMPC_SEP, IMPC_SEP_LOOP = 4, 20
 
 # the launch-uniform options of one IMPC launch, in the bit order of MPCCBF_FACT_* (mpccbf.h)
 LAUNCH_FACTS = ("targets", "traj_t", "substeps", "cov", "nb_out", "primal_res", "dual_res", "cone", "x",
-                "status", "obj", "iters", "next_states", "insert")
+                "status", "obj", "iters", "next_states", "insert", "est")
 # the closed-loop launch of run_steps in grid mode as bench.py drives it: the loop form's options
 LOOP_LAUNCH = dict.fromkeys(LAUNCH_FACTS, False)
 LOOP_LAUNCH.update(dict.fromkeys(("targets", "traj_t", "x", "status", "obj", "iters", "next_states", "insert"), True))
@@ -185,6 +185,12 @@ class Connectivity(C.Structure):
                 ("fiedler", C.c_void_p)]
 
 
+class FovEstimates(C.Structure):
+    _fields_ = [("num_pairs", C.c_int32), ("nb_xy", C.c_void_p), ("nb_cov", C.c_void_p), ("pf", C.c_void_p),
+                ("particles", C.c_void_p), ("weights", C.c_void_p), ("est_xy", C.c_void_p),
+                ("est_cov", C.c_void_p), ("flags", C.c_void_p)]
+
+
 class Run(C.Structure):
     _fields_ = [("num_steps", C.c_int32), ("states_alt", C.c_void_p), ("status_log", C.c_void_p),
                 ("iters_log", C.c_void_p), ("step_ms", C.c_void_p), ("solve_ms", C.c_void_p),
@@ -239,6 +245,8 @@ def load():
         L.mpccbf_cap_audit_run.argtypes = [vp, C.POINTER(Batch), C.POINTER(CapAudit), vp]
     if hasattr(L, "mpccbf_set_connectivity"):
         L.mpccbf_set_connectivity.argtypes = [vp, C.POINTER(Connectivity)]
+    if hasattr(L, "mpccbf_set_fov_estimates"):
+        L.mpccbf_set_fov_estimates.argtypes = [vp, C.POINTER(FovEstimates)]
     L.mpccbf_build_neighbors.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_double, vp, vp, vp]
     L.mpccbf_qp_solve_dense.argtypes = [C.POINTER(DenseQP), vp, vp, vp]
@@ -303,6 +311,9 @@ class PreparedRun:
 
     def __call__(self):
         _check(self._fn(self._ctx._h, C.byref(self._b), C.byref(self._r), self._s))
+        est = self._ctx._fov_estimator
+        if est is not None and self._b.nb_row_ptr:  # (the attached filter stepped once per step)
+            est.step_index += self._n
         out = {"final": self._tables[0] if self._r.final_table == 0 else self._tables[1]}
         if self._solve_ms is not None:
             # copies: the library overwrites both host buffers at the next call
@@ -341,6 +352,8 @@ class Context:
         self.device = device
         self._active_store = None
         self._connectivity = None
+        self._fov_estimates = None   # the tensors attached by set_fov_estimates / set_fov_estimator
+        self._fov_estimator = None   # the FovEstimator run_steps drives, or None
         self._last_knn = (0, 0.0)  # the neighbour query of the last solve (audit_neighbors' default)
 
     def close(self):
@@ -410,6 +423,49 @@ class Context:
                          fiedler=_ptr(fiedler))
         _check(load().mpccbf_set_connectivity(self._h, C.byref(k)))
         self._connectivity = (tp, lambda2, fiedler)
+
+    def _check_pair_tensor(self, name, t, cols, rows=None):
+        import torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise MpccbfError(f"{name} must be a contiguous float64 device tensor")
+        if t.device.index != self.device:
+            raise MpccbfError(f"{name} is on {t.device}, the context on device {self.device}")
+        if t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
+            raise MpccbfError(f"{name} must have shape (pairs, {cols})")
+
+    def set_fov_estimates(self, nb_xy, nb_cov=None):
+        """Attach each observer's own neighbour estimates (mpccbf_set_fov_estimates), or detach with
+        nb_xy None. nb_xy (pairs x 2) / nb_cov (pairs x 3 = (cxx, cxy, cyy), None = unknown):
+        float64 device tensors indexed by the CSR entry of the lists a later solve is given —
+        FovEstimator's est_xy / est_cov pass unchanged. While attached every FoV solve in CSR mode
+        takes pair e's neighbour position from nb_xy[e] and the slack order from nb_cov[e] (cov= is
+        ignored); the tensors are read at every solve, so writing into them updates the estimates.
+        The context keeps a reference to them while attached."""
+        if nb_xy is None:
+            _check(load().mpccbf_set_fov_estimates(self._h, None))
+            self._fov_estimates = self._fov_estimator = None
+            return
+        self._check_pair_tensor("nb_xy", nb_xy, 2)
+        if nb_cov is not None:
+            self._check_pair_tensor("nb_cov", nb_cov, 3, rows=nb_xy.shape[0])
+        e = FovEstimates(num_pairs=int(nb_xy.shape[0]), nb_xy=_ptr(nb_xy), nb_cov=_ptr(nb_cov))
+        _check(load().mpccbf_set_fov_estimates(self._h, C.byref(e)))
+        self._fov_estimates, self._fov_estimator = (nb_xy, nb_cov), None
+
+    def set_fov_estimator(self, est, use_cov: bool = True):
+        """Attach a FovEstimator's own tensors and parameters: solves read its est_xy / est_cov as
+        set_fov_estimates does, and every step of run_steps (CSR lists: the estimator's) first steps
+        the filter against the table that step reads (mpccbf_pf_step, no motion input), exactly as
+        est.step(states) followed by impc_solve; est.step_index advances by the steps run.
+        impc_solve never steps it; est.init(states) is the caller's. use_cov=False: the slack order
+        takes every covariance as unknown. Detach with set_fov_estimates(None)."""
+        if est.device != self.device:
+            raise MpccbfError(f"the estimator is on device {est.device}, the context on device {self.device}")
+        e = FovEstimates(num_pairs=int(est.rows), nb_xy=_ptr(est.est_xy), nb_cov=_ptr(est.est_cov) if use_cov else None,
+                         pf=C.addressof(est.params), particles=_ptr(est.particles), weights=_ptr(est.weights),
+                         est_xy=_ptr(est.est_xy), est_cov=_ptr(est.est_cov), flags=_ptr(est.flags))
+        _check(load().mpccbf_set_fov_estimates(self._h, C.byref(e)))
+        self._fov_estimates, self._fov_estimator = (est.est_xy, est.est_cov), est
 
     def alloc_active_store(self, num_states: int, device=None):
         """A zero-filled (num_states, 8) int32 store (no records) for set_active_store."""

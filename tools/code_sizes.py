@@ -1,7 +1,7 @@
 """Per-kernel code size and instruction hash of the IMPC and dense QP kernels (cross-compile only, no GPU): the
 device code of each translation unit that instantiates them (csrc/kernels/impc_kernel.hip, impc_store.hip,
-impc_conn.hip, impc_fov.hip; the kernels themselves are in the per-layout headers impc_dense.hpp,
-impc_sep.hpp, impc_wide_kernels.hpp), of connectivity_control.hip and of the generic dense QP path
+impc_conn.hip, impc_fov.hip, impc_fov_est.hip; the kernels themselves are in the per-layout headers impc_dense.hpp,
+impc_sep.hpp, impc_wide_kernels.hpp, impc_fov.hpp), of connectivity_control.hip and of the generic dense QP path
 (csrc/dense_qp.hip) is compiled for gfx950 on its own
 (--offload-device-only), and for every kernel symbol the table gives its size in bytes and the
 SHA-1 of its disassembled instructions (mnemonics and operands; addresses and encodings dropped).
@@ -23,7 +23,8 @@ LLVM = "/opt/rocm/llvm/bin"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
          "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 SRCS = ["csrc/kernels/impc_kernel.hip", "csrc/kernels/impc_store.hip", "csrc/kernels/impc_conn.hip",
-        "csrc/kernels/impc_fov.hip", "csrc/kernels/connectivity_control.hip", "csrc/dense_qp.hip"]
+        "csrc/kernels/impc_fov.hip", "csrc/kernels/impc_fov_est.hip", "csrc/kernels/connectivity_control.hip",
+        "csrc/dense_qp.hip"]
 
 
 def device_code(src):

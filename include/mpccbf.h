@@ -539,7 +539,20 @@ typedef struct mpccbf_fov_control_batch {
 
 /* Capacity: 4 * neighbours + 9 <= 64 rows per agent (13 observed neighbours) without slack;
  * 16 observed neighbours in slack mode (one slack variable each, cost slack_cost *
- * decay^{idx[i]}, included in obj); beyond it the agent's status is MPCCBF_ERROR. */
+ * decay^{idx[i]}, included in obj); beyond it the agent's status is MPCCBF_ERROR.
+ *
+ * (The FoV controller inside mpccbf_impc_solve / mpccbf_run_steps, cbf_mode 1, has its own capacity,
+ * per agent and IMPC iteration: 16 observed neighbours, 8 in slack mode, and 192 rows. The rows
+ * are the shared box rows (mpccbf_num_shared_rows: 72 at k_hor 20), 4 Voronoi rows per neighbour
+ * and the FoV rows the in-kernel filter keeps — at most 4 per neighbour in iteration 0 and
+ * 4 * cbf_horizon from iteration 1 on; 2 and 2 * cbf_horizon at fov_beta = 2 pi, which has no
+ * border rows; every one of them with mpccbf_options::no_cbf_filter. E.g. without the filter at
+ * cbf_horizon 2 ten neighbours fill 72 + 40 + 80 = 192 rows and eleven do not fit. In slack mode
+ * the FoV rows live in a slack image of 80 rows behind the others: box + Voronoi rows, rounded up
+ * to a multiple of 16, plus 80 must not exceed 192 — 8 neighbours at 72 box rows land on it
+ * exactly; with mpccbf_options::keep_redundant (117 box rows at k_hor 20) no neighbour count fits,
+ * not even none. An iteration over a cap reports MPCCBF_ERROR and the iterations after it
+ * UNKNOWN, the agent keeping the curve of the iterations before; other agents are unaffected.) */
 int mpccbf_fov_control_solve(const mpccbf_fov_control_params* p, const mpccbf_fov_control_batch* b,
                              int32_t device, void* hip_stream);
 

@@ -56,6 +56,8 @@ def test_regression_cases_match_oracle(mpclib):
     listed neighbours, the GPU's statuses / objectives / control points against the oracle."""
     torch = _torch()
     cases = json.load(open(os.path.join(HERE, "golden", "regress_cases.json")))["cases"]
+    # (records beyond the oracle's reach are held by the penalty objective in test_gpu_fov_params.py)
+    cases = [c for c in cases if c.get("reference") != "penalty"]
     dev = torch.device("cuda", 0)
     assert any(c.get("controller") == "fov_slack" for c in cases)
     assert any(c.get("controller") == "collision_slack" for c in cases)

@@ -33,6 +33,7 @@
 #ifndef MPCCBF_H
 #define MPCCBF_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -694,6 +695,103 @@ typedef struct mpccbf_fov_estimates {
     int32_t* flags;           /* pairs, or NULL */
 } mpccbf_fov_estimates;
 int mpccbf_set_fov_estimates(mpccbf_ctx* ctx, const mpccbf_fov_estimates* e /* NULL detaches */);
+
+/* ---- Closed-loop safety monitor (feature macro; MPCCBF_ABI_VERSION is unchanged: no struct changed
+ * layout) ------------------------------------------------------------------------------------------
+ *
+ * Scores snapshots of a swarm on the device with the semantics of the reference's post-processing
+ * script (workspace/experiments/python/metrics/collision_check.py:11-80), so a closed-loop run says
+ * whether it stayed safe without its trace leaving the device. A sample is one snapshot of every
+ * row's (x, y, ., ., ., .); samples are numbered from 0 after a reset.
+ *
+ * Per sample, over every unordered pair of rows i < j whose squared distance dx*dx + dy*dy, as
+ * computed in double (products and sum rounded separately), is <= watch_radius^2 (inclusive):
+ *   collision    box: rectangles_collide (:11-20) on the script's boxes (:28-39), term by term: corner
+ *                = centre - half / 2, extent = 2 half, strict < and >; only additions and comparisons,
+ *                so every decision is the script's, touching edges included. circle: d2 <= (2 r)^2,
+ *                where the script tests hypot(dx, dy) <= 2 r: the two can differ by one rounding for
+ *                a pair at the threshold.
+ *   inside d_min d2 < d_min^2: the pair has left the CBF's own safe set.
+ * Pairs beyond watch_radius are not seen: it must cover d_min and the shape's reach (circle 2 r, box
+ * 2 |half| (1 + 2^-20)), so no collision and no pair inside d_min is missed; min_d2 is +inf for a row
+ * with no other row that near. Goal test, agents only: dx*dx + dy*dy <= goal_radius^2 against the
+ * agent's goal (the script takes the norm; the two can differ by one rounding at the threshold).
+ *
+ * Outputs (device; all integers, accumulated by atomic add and 64-bit unsigned atomic min, so they
+ * repeat bit for bit in any order of arrival). summary, MPCCBF_MONITOR_WORDS int64:
+ *   [0]  samples scored since the reset
+ *   [1]  first collision as (sample << 40) | (i << 20) | j, the script's order (earliest sample, then
+ *        smallest i, then smallest j); -1 = none
+ *   [2]  colliding pair-samples   [3]  pair-samples inside d_min
+ *   [4]  bits of the smallest squared distance seen (a non-negative double orders as its bits); +inf
+ * Per row of the state table (index = the row's index in the table): reached_at = the first sample
+ * with the agent inside its goal area (-1: never; rows that are no agents stay -1), min_d2, hit_samples
+ * = samples in which the row is part of a colliding pair, unsafe_samples = samples with another row
+ * inside d_min. sample_log (optional): row s = (colliding pairs, pairs inside d_min, bits of the
+ * smallest squared distance) of sample s, for s < sample_log_rows.
+ *
+ * mpccbf_monitor_score scores num_samples samples of num_states rows. `samples` holds the agents'
+ * states, agent a (row agent_first + a) of sample s at samples[s * sample_stride + a * row_stride]
+ * (strides in doubles: a state table is (., 6), a mpccbf_batch::substeps buffer or a trace
+ * traj[n][ts][6] is (6, ts * 6)). fixed_states (may be NULL) is a num_states x 6 table whose rows
+ * outside the agent range take part in every sample as static rows, keeping their table index; with
+ * NULL there are no such rows. goals: num_agents x 3, or NULL for no goal scoring. sample_first: the
+ * index of the first sample, or -1 to continue at summary[0] (read on the device). Samples whose
+ * index would reach 2^23 are not scored and not counted. Each call enqueues four operations (a
+ * memset and three launches) on the stream: no host synchronisation, no allocation.
+ *
+ * One spatial hash per sample (count, scan, scatter: a cell holds any number of rows; cell edge and
+ * table size by the rules of mpccbf_build_neighbors, mpccbf_monitor_table_size(num_states) buckets),
+ * in the caller's scratch: mpccbf_monitor_scratch_bytes(rows, the most samples of one call).
+ *
+ * Refused with MPCCBF_ERR_INVALID_ARGUMENT on the host, before any device call: a NULL monitor, a
+ * missing output (summary, reached_at, min_d2, hit_samples, unsafe_samples, scratch), a bad shape
+ * (shape_type outside 0 / 1, a radius or half extent that is not positive and finite), d_min not
+ * positive and finite, goal_radius < 0, watch_radius below d_min or below the shape's reach, rows < 1,
+ * sample_log_rows < 0; at a score also negative counts, an agent range outside num_states,
+ * num_states > rows, num_states > 2^20, sample_first < -1, sample_first + num_samples > 2^23, a
+ * scratch smaller than mpccbf_monitor_scratch_bytes(num_states, num_samples), NULL samples with
+ * agents to score. num_samples == 0 or num_states == 0: MPCCBF_OK, nothing enqueued.
+ *
+ * mpccbf_set_monitor attaches a monitor (copied; its buffers stay the caller's) to a context. While
+ * attached, every mpccbf_impc_solve that is given next_states, and every step of mpccbf_run_steps,
+ * enqueues one mpccbf_monitor_score after that step's IMPC launch on the same stream: the step's
+ * substeps records (int(h / Ts) samples) when the batch gives substeps, else the one next-state
+ * sample (table T_{s+1} in mpccbf_run_steps). The other rows of the state table are the fixed rows,
+ * the goals are batch->targets (none with refs), and the sample index continues at summary[0] until
+ * mpccbf_monitor_reset. The IMPC launch is untouched: no argument is added, removed or changed, so
+ * kernel name, launch form ("loop" included) and every solve output are what they are unattached.
+ * Refused at a solve while attached: num_states > rows, a scratch too small for the step's samples,
+ * and a communicator of more than one rank. Limits: pairs beyond watch_radius are not seen, 2^20
+ * rows, 2^23 samples, a single rank. */
+#define MPCCBF_HAS_MONITOR 1
+#define MPCCBF_MONITOR_WORDS 5
+typedef struct mpccbf_monitor {
+    int32_t shape_type;      /* 0 circle, 1 box (collision_check.py:22-41) */
+    double  shape[2];        /* radius, - | half extents cx, cy as the script takes them */
+    double  d_min;           /* the CBF's safe distance */
+    double  goal_radius;     /* 0 = 1.0 (the script's default) */
+    double  watch_radius;    /* 0 = 3 d_min; >= d_min and >= the shape's reach, else INVALID_ARGUMENT */
+    int32_t rows;            /* capacity of the per-row arrays (>= num_states scored) */
+    int64_t* summary;        /* device, MPCCBF_MONITOR_WORDS: samples, first-collision key (-1),
+                                colliding pair-samples, pair-samples inside d_min, min d2 bits */
+    int64_t* reached_at;     /* device, rows: first sample inside the goal area, -1 */
+    double*  min_d2;         /* device, rows: smallest squared distance to another row, +inf beyond watch_radius */
+    int32_t* hit_samples;    /* device, rows: samples in which the row collides */
+    int32_t* unsafe_samples; /* device, rows: samples with another row inside d_min */
+    int64_t* sample_log;     /* device, sample_log_rows x 3 (hits, inside d_min, min d2 bits), or NULL */
+    int32_t  sample_log_rows;
+    void*    scratch; size_t scratch_bytes;  /* >= mpccbf_monitor_scratch_bytes(rows, max samples per call) */
+} mpccbf_monitor;
+size_t mpccbf_monitor_scratch_bytes(int32_t rows, int32_t max_samples);
+uint32_t mpccbf_monitor_table_size(int32_t num_rows);
+/* initialises every output (summary, the per-row arrays over `rows`, the sample log) */
+int mpccbf_monitor_reset(const mpccbf_monitor* m, int32_t device, void* hip_stream);
+int mpccbf_monitor_score(const mpccbf_monitor* m, const double* samples, int32_t num_samples,
+                         int64_t sample_stride, int64_t row_stride, int32_t agent_first, int32_t num_agents,
+                         const double* fixed_states, int32_t num_states, const double* goals,
+                         int64_t sample_first, int32_t device, void* hip_stream);
+int mpccbf_set_monitor(mpccbf_ctx* ctx, const mpccbf_monitor* m /* NULL detaches */);
 
 /* ---- Batched CBF-only connectivity controller (ConnectivityControl::optimize,
  * cbf/src/controller/ConnectivityControl.cpp:22-99) for teams of robots ----------------------

@@ -27,6 +27,7 @@
 #include "kernels/cap_audit.hpp"
 #include "kernels/conn_rows.hpp"
 #include "kernels/launch_plan.hpp"
+#include "kernels/monitor.hpp"
 #include "kernels/pf_fov.hpp"
 
 namespace mpccbf {
@@ -122,6 +123,12 @@ struct mpccbf_ctx {
         mpccbf_fov_estimates e{};
         mpccbf_pf_params pf{};
     } est;
+    // safety monitor (mpccbf_set_monitor): the caller's monitor as attached (its buffers stay the
+    // caller's); every step's samples are scored after the step's IMPC launch (monitor_after_step)
+    struct {
+        bool on = false;
+        mpccbf_monitor m{};
+    } mon;
 };
 
 using namespace mpccbf;
@@ -382,6 +389,30 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
 }
 
 
+// The attached monitor's score of the step `b` just enqueued, behind its IMPC launch on the same
+// stream: the step's sub-step records when the batch gives them, else its one next-state sample.
+// The rows outside the agent range are those of the table the step read. The IMPC launch itself is
+// untouched (nothing here is an argument of it).
+// What the attached monitor refuses of a batch, ahead of the step's launches
+static int monitor_step_check(const mpccbf_ctx* c, const mpccbf_batch* b) {
+    if (!c->mon.on || b->num_agents <= 0) return MPCCBF_OK;
+    const mpccbf_monitor& m = c->mon.m;
+    if (b->num_states > m.rows || b->num_states > MONITOR_MAX_ROWS)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: rows (" + std::to_string(m.rows) + ") < num_states (" +
+                                                     std::to_string(b->num_states) + ")");
+    if (monitor_scratch_bytes(b->num_states, b->substeps ? c->dev.nsub : 1) > m.scratch_bytes)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: scratch too small for this step's samples");
+    return MPCCBF_OK;
+}
+
+static int monitor_after_step(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream) {
+    if (!c->mon.on || !b->next_states || b->num_agents <= 0) return MPCCBF_OK;
+    const bool sub = b->substeps != nullptr;
+    const int nsub = c->dev.nsub;
+    return monitor_enqueue(&c->mon.m, sub ? b->substeps : b->next_states, sub ? nsub : 1, 6, sub ? (int64_t)nsub * 6 : 6,
+                           b->agent_first, b->num_agents, b->states, b->num_states, b->targets, -1, c->device, stream);
+}
+
 extern "C" {
 
 int mpccbf_abi_version(void) { return MPCCBF_ABI_VERSION; }
@@ -456,7 +487,13 @@ int mpccbf_num_shared_rows(const mpccbf_ctx* c) { return c ? c->ops.G.r : -1; }
 
 int mpccbf_impc_solve(mpccbf_ctx* c, const mpccbf_batch* b, void* stream) {
     if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    return impc_enqueue(c, b, (hipStream_t)stream, nullptr, nullptr, c->dev, c->store);
+    if (b && b->next_states) {
+        const int mrc = monitor_step_check(c, b);
+        if (mrc != MPCCBF_OK) return mrc;
+    }
+    const int rc = impc_enqueue(c, b, (hipStream_t)stream, nullptr, nullptr, c->dev, c->store);
+    if (rc != MPCCBF_OK || !b) return rc;
+    return monitor_after_step(c, b, (hipStream_t)stream);
 }
 
 // (the clock waves do not depend on where the neighbour lists come from: the dense layouts, whose
@@ -540,6 +577,18 @@ int mpccbf_set_fov_estimates(mpccbf_ctx* c, const mpccbf_fov_estimates* e) {
         c->est.pf = *e->pf;
         c->est.e.pf = &c->est.pf;
     }
+    return MPCCBF_OK;
+}
+
+int mpccbf_set_monitor(mpccbf_ctx* c, const mpccbf_monitor* m) {
+    // the checks that need no context first
+    if (m) {
+        const std::string err = monitor_attach_error(m);
+        if (!err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, err);
+    }
+    if (!c) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null context");
+    c->mon.on = m != nullptr;
+    c->mon.m = m ? *m : mpccbf_monitor{};
     return MPCCBF_OK;
 }
 
@@ -771,6 +820,9 @@ void mpccbf_comm_destroy(mpccbf_comm* cm) {
 
 int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* stream_) {
     if (!c || !b || !r) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
+    // (before the group's first barrier: a refused rank never joins it)
+    if (c->mon.on && r->comm && r->comm->nranks > 1)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: a communicator of more than one rank is not supported");
     // in-process group: any return before the last step's barrier aborts the group (the peers
     // get an error), and every rank must run the same number of steps
     LocalGroup* lg = (r->comm && r->comm->nranks > 1 && r->comm->local) ? r->comm->local.get() : nullptr;
@@ -805,6 +857,10 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
     {
         const std::string est_err = fov_estimates_solve_error(c->est.on, false, r->comm ? r->comm->nranks : 1);
         if (!est_err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, est_err);
+    }
+    if (r->num_steps > 0) {
+        const int mrc = monitor_step_check(c, b);
+        if (mrc != MPCCBF_OK) return mrc;
     }
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
@@ -888,6 +944,9 @@ int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* 
                                                           2 * (size_t)r->kernel_clock_waves * s
                                                     : nullptr);
         if (rc != MPCCBF_OK) return rc;
+        // (a single rank: the table of the next step is complete behind the IMPC launch)
+        const int mrc = monitor_after_step(c, &sb, stream);
+        if (mrc != MPCCBF_OK) return mrc;
         if (r->comm && r->comm->nranks > 1 && r->comm->local) {
             // in-process group: every rank's block of this step copied into this rank's table
             LocalGroup& g = *r->comm->local;

@@ -1,7 +1,8 @@
 // capi_control.hip — the C ABI's entry points that hold no context: the CBF-only controllers
 // (mpccbf_connectivity_control_solve, mpccbf_fov_rows_eval, mpccbf_fov_control_solve) and the FoV
-// particle filter (mpccbf_pf_init, mpccbf_pf_step). Each checks its arguments on the host, fills the
-// kernel's argument struct and enqueues one launch.
+// particle filter (mpccbf_pf_init, mpccbf_pf_step) and the safety monitor (mpccbf_monitor_reset,
+// mpccbf_monitor_score). Each checks its arguments on the host, fills the kernel's argument struct
+// and enqueues its launches.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,7 +13,9 @@
 #include "host/fov_estimates.hpp"
 #include "host/hip_host.hpp"
 #include "kernels/cbf_control.hpp"
+#include "kernels/impc.hpp"
 #include "kernels/launch_plan.hpp"
+#include "kernels/monitor.hpp"
 #include "kernels/pf_fov.hpp"
 
 using namespace mpccbf;
@@ -206,6 +209,142 @@ int mpccbf_pf_init(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t 
 
 int mpccbf_pf_step(const mpccbf_pf_params* p, const mpccbf_pf_batch* b, int32_t device, void* stream) {
     return pf_enqueue(p, b, device, stream, false, 0);
+}
+
+}  // extern "C"
+
+// ---- safety monitor ------------------------------------------------------------------------------
+
+// The monitor's own fields (what mpccbf_set_monitor, mpccbf_monitor_reset and mpccbf_monitor_score
+// all refuse): empty when they are good. watch: the watch radius with its default applied.
+static std::string monitor_error(const mpccbf_monitor* m, double* watch) {
+    if (!m) return "monitor: null monitor";
+    if (m->shape_type != 0 && m->shape_type != 1) return "monitor: shape_type must be 0 (circle) or 1 (box)";
+    if (!(m->shape[0] > 0.0) || !std::isfinite(m->shape[0]))
+        return "monitor: the shape's radius / half extent must be positive and finite";
+    if (m->shape_type == 1 && (!(m->shape[1] > 0.0) || !std::isfinite(m->shape[1])))
+        return "monitor: the box's half extents must be positive and finite";
+    if (!(m->d_min > 0.0) || !std::isfinite(m->d_min)) return "monitor: d_min must be positive and finite";
+    if (!(m->goal_radius >= 0.0) || !std::isfinite(m->goal_radius)) return "monitor: goal_radius must be >= 0 and finite";
+    const double w = m->watch_radius == 0.0 ? 3.0 * m->d_min : m->watch_radius;
+    // the largest centre distance at which the shape test can hold (box: offsets below 2 half on both
+    // axes, with room for the roundings of the script's corner arithmetic)
+    const double reach = m->shape_type == 1 ? 2.0 * std::hypot(m->shape[0], m->shape[1]) * (1.0 + 0x1p-20) : 2.0 * m->shape[0];
+    if (!std::isfinite(w) || !(w >= m->d_min) || !(w >= reach))
+        return "monitor: watch_radius must cover d_min and the shape's reach";
+    if (m->rows < 1) return "monitor: rows must be >= 1";
+    if (!m->summary || !m->reached_at || !m->min_d2 || !m->hit_samples || !m->unsafe_samples)
+        return "monitor: summary, reached_at, min_d2, hit_samples and unsafe_samples are required";
+    if (!m->scratch) return "monitor: scratch is required";
+    if (m->sample_log_rows < 0 || (m->sample_log && m->sample_log_rows == 0))
+        return "monitor: a sample log needs sample_log_rows >= 1";
+    *watch = w;
+    return "";
+}
+
+static void monitor_outputs(const mpccbf_monitor* m, MonitorArgs& a) {
+    a.summary = (unsigned long long*)m->summary;
+    a.reached_at = (unsigned long long*)m->reached_at;
+    a.min_d2 = (unsigned long long*)m->min_d2;
+    a.hit_samples = (uint32_t*)m->hit_samples;
+    a.unsafe_samples = (uint32_t*)m->unsafe_samples;
+    a.sample_log = (unsigned long long*)m->sample_log;
+    a.sample_log_rows = m->sample_log ? m->sample_log_rows : 0;
+}
+
+std::string mpccbf::monitor_attach_error(const mpccbf_monitor* m) {
+    double w;
+    return monitor_error(m, &w);
+}
+
+int mpccbf::monitor_enqueue(const mpccbf_monitor* m, const double* samples, int32_t num_samples, int64_t sample_stride,
+                            int64_t row_stride, int32_t agent_first, int32_t num_agents, const double* fixed_states,
+                            int32_t num_states, const double* goals, int64_t sample_first, int32_t device,
+                            void* stream) {
+    double watch = 0.0;
+    const std::string merr = monitor_error(m, &watch);
+    if (!merr.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, merr);
+    if (num_samples < 0 || num_states < 0 || num_agents < 0 || agent_first < 0)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: negative count");
+    if ((int64_t)agent_first + num_agents > num_states)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: agent_first + num_agents exceeds num_states");
+    if (num_states > MONITOR_MAX_ROWS) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: num_states > 2^20");
+    if (num_states > m->rows)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: rows (" + std::to_string(m->rows) + ") < num_states (" +
+                                                     std::to_string(num_states) + ")");
+    if (sample_first < -1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: sample_first < -1");
+    if (sample_first >= 0 && sample_first + (int64_t)num_samples > MONITOR_MAX_SAMPLES)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: sample_first + num_samples > 2^23");
+    if (num_samples == 0 || num_states == 0) return MPCCBF_OK;
+    if (monitor_scratch_bytes(num_states, num_samples) > m->scratch_bytes)
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT,
+                    "monitor: scratch_bytes (" + std::to_string(m->scratch_bytes) + ") < " +
+                        std::to_string(monitor_scratch_bytes(num_states, num_samples)) + " for " +
+                        std::to_string(num_states) + " rows x " + std::to_string(num_samples) + " samples");
+    if (num_agents > 0 && !samples) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: samples is required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    MonitorArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.samples = samples;
+    a.num_samples = num_samples;
+    a.sample_stride = sample_stride;
+    a.row_stride = row_stride;
+    a.agent_first = agent_first;
+    a.num_agents = num_agents;
+    a.fixed = fixed_states;
+    a.num_states = num_states;
+    a.goals = goals;
+    a.sample_first = sample_first;
+    a.box = m->shape_type == 1;
+    a.half_x = m->shape[0];
+    a.half_y = m->shape[1];
+    a.dmin2 = m->d_min * m->d_min;
+    const double gr = m->goal_radius == 0.0 ? 1.0 : m->goal_radius;
+    a.goal2 = gr * gr;
+    a.watch2 = watch * watch;
+    a.inv_cell = grid_inv_cell(watch);
+    a.mask = monitor_table_size(num_states) - 1u;
+    monitor_outputs(m, a);
+    monitor_carve(m->scratch, num_states, num_samples, a);
+    HIP_TRY(launch_monitor_score(a, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+extern "C" {
+
+size_t mpccbf_monitor_scratch_bytes(int32_t rows, int32_t max_samples) {
+    if (rows < 0 || rows > MONITOR_MAX_ROWS || max_samples < 0) return 0;
+    return monitor_scratch_bytes(rows, max_samples);
+}
+
+uint32_t mpccbf_monitor_table_size(int32_t num_rows) {
+    return monitor_table_size(num_rows < 0 ? 0 : (num_rows > MONITOR_MAX_ROWS ? MONITOR_MAX_ROWS : num_rows));
+}
+
+int mpccbf_monitor_reset(const mpccbf_monitor* m, int32_t device, void* stream) {
+    double watch = 0.0;
+    const std::string merr = monitor_error(m, &watch);
+    if (!merr.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, merr);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    MonitorArgs a;
+    std::memset(&a, 0, sizeof(a));
+    monitor_outputs(m, a);
+    HIP_TRY(launch_monitor_reset(a, m->rows, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+int mpccbf_monitor_score(const mpccbf_monitor* m, const double* samples, int32_t num_samples, int64_t sample_stride,
+                         int64_t row_stride, int32_t agent_first, int32_t num_agents, const double* fixed_states,
+                         int32_t num_states, const double* goals, int64_t sample_first, int32_t device,
+                         void* stream) {
+    return monitor_enqueue(m, samples, num_samples, sample_stride, row_stride, agent_first, num_agents, fixed_states,
+                           num_states, goals, sample_first, device, stream);
 }
 
 }  // extern "C"

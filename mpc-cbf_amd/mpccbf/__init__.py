@@ -12,6 +12,8 @@ from ._lib import (  # noqa: F401
     PfParams, PfBatch, pf_params, pf_init, pf_step,
 )
 from . import swarm  # noqa: F401
+from . import monitor  # noqa: F401
+from .monitor import SafetyMonitor  # noqa: F401
 from .estimator import FovEstimator  # noqa: F401
 from .fov_control_sim import FovControlLoop  # noqa: F401
 from .fov_impc_sim import FovImpcLoop  # noqa: F401

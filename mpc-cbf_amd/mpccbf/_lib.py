@@ -25,7 +25,8 @@ EXPORTED = [
     "mpccbf_comm_create_local", "mpccbf_fov_rows_eval", "mpccbf_impc_launch_waves",
     "mpccbf_set_active_store", "mpccbf_cap_audit_run", "mpccbf_set_connectivity",
     "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step", "mpccbf_launch_form",
-    "mpccbf_host_launch_form", "mpccbf_set_fov_estimates",
+    "mpccbf_host_launch_form", "mpccbf_set_fov_estimates", "mpccbf_monitor_scratch_bytes",
+    "mpccbf_monitor_table_size", "mpccbf_monitor_reset", "mpccbf_monitor_score", "mpccbf_set_monitor",
 ]
 
 # ImpcKernel ids (csrc/kernels/launch_plan.hpp) of the 16-lane main launch: generic and loop form
@@ -191,6 +192,18 @@ class FovEstimates(C.Structure):
                 ("est_cov", C.c_void_p), ("flags", C.c_void_p)]
 
 
+# safety monitor (mpccbf_monitor): int64 words of its summary
+MONITOR_WORDS = 5
+
+
+class Monitor(C.Structure):
+    _fields_ = [("shape_type", C.c_int32), ("shape", C.c_double * 2), ("d_min", C.c_double),
+                ("goal_radius", C.c_double), ("watch_radius", C.c_double), ("rows", C.c_int32),
+                ("summary", C.c_void_p), ("reached_at", C.c_void_p), ("min_d2", C.c_void_p),
+                ("hit_samples", C.c_void_p), ("unsafe_samples", C.c_void_p), ("sample_log", C.c_void_p),
+                ("sample_log_rows", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
 class Run(C.Structure):
     _fields_ = [("num_steps", C.c_int32), ("states_alt", C.c_void_p), ("status_log", C.c_void_p),
                 ("iters_log", C.c_void_p), ("step_ms", C.c_void_p), ("solve_ms", C.c_void_p),
@@ -247,6 +260,15 @@ def load():
         L.mpccbf_set_connectivity.argtypes = [vp, C.POINTER(Connectivity)]
     if hasattr(L, "mpccbf_set_fov_estimates"):
         L.mpccbf_set_fov_estimates.argtypes = [vp, C.POINTER(FovEstimates)]
+    if hasattr(L, "mpccbf_set_monitor"):  # (MPCCBF_LIB may name a library from before the monitor)
+        L.mpccbf_set_monitor.argtypes = [vp, C.POINTER(Monitor)]
+        L.mpccbf_monitor_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.mpccbf_monitor_scratch_bytes.restype = C.c_size_t
+        L.mpccbf_monitor_table_size.argtypes = [C.c_int32]
+        L.mpccbf_monitor_table_size.restype = C.c_uint32
+        L.mpccbf_monitor_reset.argtypes = [C.POINTER(Monitor), C.c_int32, vp]
+        L.mpccbf_monitor_score.argtypes = [C.POINTER(Monitor), vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                           C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp]
     L.mpccbf_build_neighbors.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_double, vp, vp, vp]
     L.mpccbf_qp_solve_dense.argtypes = [C.POINTER(DenseQP), vp, vp, vp]
@@ -354,6 +376,7 @@ class Context:
         self._connectivity = None
         self._fov_estimates = None   # the tensors attached by set_fov_estimates / set_fov_estimator
         self._fov_estimator = None   # the FovEstimator run_steps drives, or None
+        self._monitor = None         # the attached SafetyMonitor, or None
         self._last_knn = (0, 0.0)  # the neighbour query of the last solve (audit_neighbors' default)
 
     def close(self):
@@ -467,6 +490,26 @@ class Context:
         _check(load().mpccbf_set_fov_estimates(self._h, C.byref(e)))
         self._fov_estimates, self._fov_estimator = (est.est_xy, est.est_cov), est
 
+    def set_monitor(self, mon):
+        """Attach a SafetyMonitor (mpccbf_set_monitor), or detach with None. While attached, every
+        impc_solve that is given next_states and every step of run_steps enqueues one score of that
+        step's samples behind its IMPC launch: the substeps records when substeps= is given, else
+        the next states; the goals are targets=. The IMPC launch itself is unchanged. The context
+        keeps a reference to the monitor while it is attached."""
+        if mon is None:
+            _check(load().mpccbf_set_monitor(self._h, None))
+            self._monitor = None
+            return
+        if mon.device != self.device:
+            raise MpccbfError(f"the monitor is on device {mon.device}, the context on device {self.device}")
+        _check(load().mpccbf_set_monitor(self._h, C.byref(mon.struct)))
+        self._monitor = mon
+
+    def _monitor_agents(self, agent_first, num_agents, scored):
+        # (the attached monitor's result() takes its goal statistics over the agents last scored)
+        if self._monitor is not None and scored and num_agents > 0:
+            self._monitor.agents = (int(agent_first), int(num_agents))
+
     def alloc_active_store(self, num_states: int, device=None):
         """A zero-filled (num_states, 8) int32 store (no records) for set_active_store."""
         import torch
@@ -509,6 +552,7 @@ class Context:
                   cov=_ptr(cov), primal_res=_ptr(primal_res), dual_res=_ptr(dual_res),
                   substeps=_ptr(substeps), nb_out=_ptr(nb_out))
         _check(load().mpccbf_impc_solve(self._h, C.byref(b), _stream(stream)))
+        self._monitor_agents(agent_first, num_agents, next_states is not None)
 
     def audit_neighbors(self, states, *, x, status, targets=None, refs=None, nb_row_ptr=None, nb_col=None,
                         nb_out=None, agent_first=0, num_agents=None, knn_k=None, knn_radius=None, tol=0.0,
@@ -554,7 +598,8 @@ class Context:
                   status=None, obj=None, iters=None, status_log=None, iters_log=None,
                   timing=False, comm=None, reserve_steps=0, solve_stride=1, step_timing=True,
                   stream=None, traj_t=None, pos_std=0.0, vel_std=0.0, noise_seed=0, step_index=0,
-                  cov=None, kernel_clock=None, stamps=None, continue_tables=False, nb_out=None):
+                  cov=None, kernel_clock=None, stamps=None, continue_tables=False, nb_out=None,
+                  substeps=None):
         """The arguments of one mpccbf_run_steps call, marshalled once (checks, ctypes structures,
         the stream handle): returns a PreparedRun whose call () runs the steps — a caller that
         times the steps prepares them outside its timed region. The call returns a dict with the
@@ -564,7 +609,8 @@ class Context:
         wave's start / end of every IMPC launch (s_memrealtime, 100 MHz ticks; zero: no wave);
         kernel_clock_us() turns it into per-launch durations. stamps: the diagnostics builds' phase
         stamps (as impc_solve; every step overwrites them). nb_out: as impc_solve (every step
-        overwrites it: it ends holding the lists of the last step)."""
+        overwrites it: it ends holding the lists of the last step). substeps: as impc_solve (every
+        step overwrites it; an attached monitor scores each step's records before the next step)."""
         if num_agents is None:
             num_agents = states.shape[0] - agent_first
         self._last_knn = (int(knn_k), float(knn_radius))
@@ -582,7 +628,8 @@ class Context:
                   knn_k=int(knn_k), knn_radius=float(knn_radius), stamps=_ptr(stamps),
                   traj_t=_ptr(traj_t), pos_std=float(pos_std), vel_std=float(vel_std),
                   noise_seed=int(noise_seed), step_index=int(step_index), cov=_ptr(cov),
-                  nb_out=_ptr(nb_out))
+                  nb_out=_ptr(nb_out), substeps=_ptr(substeps))
+        self._monitor_agents(agent_first, num_agents, num_steps > 0)
         step_ms = np.zeros(max(num_steps, 1), dtype=np.float32) if timing and step_timing else None
         solve_ms = np.zeros(max(num_steps, 1), dtype=np.float32) if timing else None
         r = Run(num_steps=num_steps, states_alt=_ptr(states_alt), status_log=_ptr(status_log),
@@ -595,7 +642,7 @@ class Context:
                 continue_tables=int(bool(continue_tables)))
         return PreparedRun(self, b, r, _stream(stream), states, states_alt, num_steps, step_ms, solve_ms,
                            keep=(targets, refs, nb_row_ptr, nb_col, x, status, obj, iters, status_log,
-                                 iters_log, traj_t, cov, kernel_clock, stamps, nb_out))
+                                 iters_log, traj_t, cov, kernel_clock, stamps, nb_out, substeps))
 
     def launch_waves(self, num_agents: int) -> int:
         """Waves of the IMPC launch for num_agents that write the launch clock (0: no clock)."""

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import swarm
 from ._lib import Context, audit_summary
+from .monitor import SafetyMonitor
 
 
 def bezier_positions(cfg: dict, x: np.ndarray, ts) -> np.ndarray:
@@ -65,12 +66,17 @@ class Simulator:
     teams / d_max: attach the connectivity-maintenance rows (Context.set_connectivity; teams = the
     team_ptr offsets into the robots, lambda2_min / lambda2_switch as there); self.lambda2_log gets
     one array per step, the lambda2 of every team at the states that step planned from. Collision
-    controller without slack variables, Jacobi order, no audit."""
+    controller without slack variables, Jacobi order, no audit.
+    monitor: True (a SafetyMonitor over the robots: box shape [0.2, 0.2], d_min of the configuration,
+    goal radius 1) or a SafetyMonitor of at least n rows, attached to the context
+    (Context.set_monitor): every step's sub-step records, the samples states_json() holds, are scored
+    on the device behind the step's solve; self.monitor.result() is metrics.instance_success of the
+    trace so far. Jacobi order. Statuses, trajectories and states_json() are those of monitor=False."""
 
     def __init__(self, cfg: dict, states: np.ndarray, targets: np.ndarray, *, neighbours="knn",
                  knn_k=8, knn_radius=None, pos_std=0.0, vel_std=0.0, noise_seed=0, device=0,
                  record=True, order="jacobi", warm=False, audit=False, teams=None, d_max=None,
-                 lambda2_min=0.1, lambda2_switch=0.1):
+                 lambda2_min=0.1, lambda2_switch=0.1, monitor=None):
         import torch
         if order not in ("jacobi", "gauss_seidel"):
             raise ValueError("order must be 'jacobi' or 'gauss_seidel'")
@@ -80,6 +86,8 @@ class Simulator:
             raise ValueError("audit=True needs the collision controller without slack variables")
         if teams is not None and (order != "jacobi" or audit):
             raise ValueError("teams needs order='jacobi' and audit=False")
+        if monitor and order != "jacobi":
+            raise ValueError("monitor needs order='jacobi'")
         if teams is not None and d_max is None:
             raise ValueError("teams needs d_max")
         self.order = order
@@ -121,6 +129,11 @@ class Simulator:
             self.ctx.set_connectivity(teams, d_max, lambda2_min=lambda2_min, lambda2_switch=lambda2_switch,
                                       lambda2=self.lambda2)
             self.num_teams = len(teams) - 1
+        self.monitor = None
+        if monitor:
+            self.monitor = (SafetyMonitor(n, d_min=cfg["d_min"], device=device, max_samples=max(self.nsub, 1))
+                            if monitor is True else monitor)
+            self.ctx.set_monitor(self.monitor)
         self.gs_next = torch.empty((1, 6), dtype=torch.float64, device=self.dev)
         self.noise = dict(pos_std=pos_std, vel_std=vel_std, noise_seed=noise_seed)
         self.step_index = 0

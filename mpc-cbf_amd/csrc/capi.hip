@@ -1,14 +1,12 @@
-// capi.hip — the C ABI of include/mpccbf.h: context lifetime, operator upload, launches (the entry
-// points that hold no context: capi_control.hip). No exception crosses this boundary (the
-// reference's std::invalid_argument / runtime_error become MPCCBF_ERR_INVALID_ARGUMENT plus a
-// thread-local message).
+// capi.hip — the C ABI of include/mpccbf.h for a context: its lifetime, operator upload, setters and
+// single launches, and impc_enqueue, the one IMPC step that every launch path goes through
+// (the communicators and mpccbf_run_steps: capi_run.hip, which shares capi_ctx.hpp with this
+// unit; the entry points that hold no context: capi_control.hip). No exception crosses this
+// boundary (the reference's std::invalid_argument / runtime_error become
+// MPCCBF_ERR_INVALID_ARGUMENT plus a thread-local message).
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -16,19 +14,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/mpccbf.h"
-#include "host/defer_queues.hpp"
+#include "capi_ctx.hpp"
 #include "host/fov_estimates.hpp"
-#include "host/grid_rotation.hpp"
-#include "host/hip_host.hpp"
-#include "host/operators.hpp"
 #include "host/pack_operators.hpp"
-#include "kernels/impc.hpp"
 #include "kernels/cap_audit.hpp"
 #include "kernels/conn_rows.hpp"
-#include "kernels/launch_plan.hpp"
 #include "kernels/monitor.hpp"
-#include "kernels/pf_fov.hpp"
 
 namespace mpccbf {
 
@@ -39,106 +30,9 @@ int set_error(int code, const std::string& msg) {
     return code;
 }
 
-// Grid mode's three neighbour tables (GridArgs) in one buffer grown on demand, with the rotation
-// that says which of them a step uses and what a later call may continue (grid_rotation.hpp). The
-// device calls are here; every decision, and the only writes of the continuation record, are rot's.
-struct GridTables {
-    DevBuf buf;
-    GridRotation rot;
-    uint32_t *cnt[3] = {}, *slots[3] = {};
-    double* sst[3] = {};
-
-    // the tables of a state table of num_states rows
-    int carve(int num_states) {
-        const size_t tb = grid_table_bytes(num_states);
-        rot.reallocates(3 * tb, buf.bytes);
-        HIP_TRY(buf.reserve(3 * tb));
-        for (int t = 0; t < 3; t++)
-            grid_table_carve(buf.as<char>() + t * tb, num_states, &cnt[t], &slots[t], &sst[t]);
-        return MPCCBF_OK;
-    }
-    // table 0 from these states; zero_fill: table 1 zeroed for the inserts of the step that reads it
-    int rebuild(const double* states, int num_states, double radius, bool zero_fill, hipStream_t stream) {
-        const size_t cb = (size_t)grid_table_size(num_states) * 4;
-        HIP_TRY(hipMemsetAsync(cnt[0], 0, cb, stream));
-        if (zero_fill) HIP_TRY(hipMemsetAsync(cnt[1], 0, cb, stream));
-        HIP_TRY(launch_grid_insert(states, num_states, 0, 0, radius, cnt[0], slots[0], sst[0], stream));
-        return MPCCBF_OK;
-    }
-};
-
-// What the last IMPC launch was, for the calls that report it (mpccbf_kernel_name: the name is
-// share-adaptive in the agents, and the default variant's dense layout depends on where the
-// neighbour lists come from; mpccbf_launch_form)
-struct LastLaunch {
-    int n = 0;
-    bool csr = false;
-    int knn = 0;
-    LaunchForm form = FORM_GENERIC;
-};
-
 }  // namespace mpccbf
 
-struct mpccbf_ctx {
-    std::vector<hipEvent_t> events;  // timing events of mpccbf_run_steps (grown on demand)
-    mpccbf_params p;
-    mpccbf_options opt;
-    mpccbf::Operators ops;
-    mpccbf::DevOps dev;
-    int device = 0;
-    mpccbf::DevBuf dbuf;          // the packed operators (pack_operators)
-    mpccbf::DevBuf scratch;       // mpccbf_build_neighbors
-    mpccbf::GridTables grid;      // grid mode's neighbour tables and their rotation
-    // the two deferral queues (defer_queues.hpp: offsets into defer)
-    mpccbf::DevBuf defer;
-    mpccbf::DeferQueues queues;
-    int variant = 0;
-    mpccbf::LastLaunch last;
-    // active-set store (mpccbf_set_active_store): the caller's device buffer of store_rows records,
-    // or nullptr; store_min_steps as the kernels take it (>= 1, or < 0: export only)
-    int32_t* store = nullptr;
-    int store_rows = 0;
-    int store_min_steps = 0;
-    // neighbour-cap audit (mpccbf_cap_audit_run): the second-derivative basis' offset in dbuf, and
-    // the scratch its iteration-0 launch writes (x0: agents x n doubles, then their statuses)
-    int32_t o_EB2 = 0;
-    mpccbf::DevBuf audit_scratch;
-    // connectivity rows (mpccbf_set_connectivity): the teams (host copy), the caller's outputs, and
-    // the device tables the spectrum launch fills per step and the IMPC launch reads (ConnArgs;
-    // allocated at the first solve, rows: the state rows they cover)
-    struct {
-        bool on = false;
-        double dmax = 0.0, l2_min = 0.1, l2_switch = 0.1;
-        std::vector<int32_t> team_ptr;
-        double* out_l2 = nullptr;
-        double* out_fiedler = nullptr;
-        int rows = 0;
-        mpccbf::DevBuf d_team_ptr, d_team_mode, d_row_team;  // int32
-        mpccbf::DevBuf d_team_l2, d_fiedler;                 // double
-    } conn;
-    // per-pair neighbour estimates (mpccbf_set_fov_estimates): the caller's buffers as attached
-    // (e.pf: null, or &pf, the copied filter parameters mpccbf_run_steps steps the filter with)
-    struct {
-        bool on = false;
-        mpccbf_fov_estimates e{};
-        mpccbf_pf_params pf{};
-    } est;
-    // safety monitor (mpccbf_set_monitor): the caller's monitor as attached (its buffers stay the
-    // caller's); every step's samples are scored after the step's IMPC launch (monitor_after_step)
-    struct {
-        bool on = false;
-        mpccbf_monitor m{};
-    } mon;
-};
-
 using namespace mpccbf;
-
-// The launch plan of the context's next IMPC step for n agents (launch_plan.hpp)
-static LaunchPlan ctx_plan(const mpccbf_ctx* c, int n, bool csr, int knn_k, bool store) {
-    LaunchFacts f{};
-    f.est = c->est.on;
-    return impc_launch_plan(c->dev, c->variant, n, csr, knn_k, store, c->conn.on, f);
-}
 
 // Warm-start threshold when mpccbf_set_active_store is given min_steps = 0
 constexpr int STORE_MIN_STEPS_DEFAULT = 3;
@@ -176,9 +70,15 @@ static int conn_tables(mpccbf_ctx* c, int num_states) {
 
 // ---- the steps of impc_enqueue, in its order ---------------------------------------------------
 
-static int check_agent_range(const mpccbf_batch* b) {
+int mpccbf::check_agent_range(const mpccbf_batch* b) {
     if (b->num_agents < 0 || b->agent_first < 0 || b->agent_first + b->num_agents > b->num_states)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent range outside states");
+    return MPCCBF_OK;
+}
+
+int mpccbf::check_grid_query(const mpccbf_batch* b) {
+    if (b->knn_k < 1 || !(b->knn_radius > 0))
+        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "grid neighbours need knn_k >= 1 and knn_radius > 0");
     return MPCCBF_OK;
 }
 
@@ -186,8 +86,8 @@ static int check_agent_range(const mpccbf_batch* b) {
 static int check_batch(const mpccbf_ctx* c, const mpccbf_batch* b, bool grid, const int32_t* store) {
     if (!b->states || (!grid && !b->nb_col && b->num_states > 1))
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "states / neighbour CSR missing");
-    if (grid && (b->knn_k < 1 || !(b->knn_radius > 0)))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "grid neighbours need knn_k >= 1 and knn_radius > 0");
+    const int grc = grid ? check_grid_query(b) : MPCCBF_OK;
+    if (grc != MPCCBF_OK) return grc;
     if (grid && b->knn_k > NB_MAX)
         return fail(MPCCBF_ERR_INVALID_ARGUMENT, "grid neighbours: knn_k > 16 not supported (give CSR lists)");
     if (!b->targets && !b->refs) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "targets or refs required");
@@ -308,12 +208,9 @@ static int defer_args(mpccbf_ctx* c, int num_agents, hipStream_t stream, ImpcArg
     return MPCCBF_OK;
 }
 
-// One IMPC step for a batch, enqueued on `stream`; ev0 / ev1 (optional) are recorded around the
-// IMPC kernel alone. run_step >= 0: step run_step of the grid-mode mpccbf_run_steps call that
-// started the rotation (GridRotation::step); < 0: a step outside a rotation (foreign_step).
-// ops / store: the context's (c->dev, c->store), or what the cap audit puts in their place.
-int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                 const DevOps& ops, int32_t* store, int run_step = -1, unsigned long long* kclock = nullptr) {
+// One IMPC step for a batch (the arguments: capi_ctx.hpp)
+int mpccbf::impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                         const DevOps& ops, int32_t* store, int run_step, unsigned long long* kclock) {
     if (!c || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
     const GridRoles roles = run_step < 0 ? c->grid.rot.foreign_step() : c->grid.rot.step(run_step);
     // validate
@@ -388,13 +285,9 @@ int impc_enqueue(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream, hipEv
     return MPCCBF_OK;
 }
 
+// ---- the attached monitor around a step (capi_ctx.hpp) ------------------------------------------
 
-// The attached monitor's score of the step `b` just enqueued, behind its IMPC launch on the same
-// stream: the step's sub-step records when the batch gives them, else its one next-state sample.
-// The rows outside the agent range are those of the table the step read. The IMPC launch itself is
-// untouched (nothing here is an argument of it).
-// What the attached monitor refuses of a batch, ahead of the step's launches
-static int monitor_step_check(const mpccbf_ctx* c, const mpccbf_batch* b) {
+int mpccbf::monitor_step_check(const mpccbf_ctx* c, const mpccbf_batch* b) {
     if (!c->mon.on || b->num_agents <= 0) return MPCCBF_OK;
     const mpccbf_monitor& m = c->mon.m;
     if (b->num_states > m.rows || b->num_states > MONITOR_MAX_ROWS)
@@ -405,7 +298,7 @@ static int monitor_step_check(const mpccbf_ctx* c, const mpccbf_batch* b) {
     return MPCCBF_OK;
 }
 
-static int monitor_after_step(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream) {
+int mpccbf::monitor_after_step(mpccbf_ctx* c, const mpccbf_batch* b, hipStream_t stream) {
     if (!c->mon.on || !b->next_states || b->num_agents <= 0) return MPCCBF_OK;
     const bool sub = b->substeps != nullptr;
     const int nsub = c->dev.nsub;
@@ -477,8 +370,7 @@ int mpccbf_create(const mpccbf_params* p, const mpccbf_options* opt, mpccbf_ctx*
 
 void mpccbf_destroy(mpccbf_ctx* c) {
     if (!c) return;
-    for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    delete c;  // (its device buffers with it)
+    delete c;  // (its device buffers and timing events with it)
 }
 
 int mpccbf_num_vars(const mpccbf_ctx* c) { return c ? c->ops.n : -1; }
@@ -693,309 +585,6 @@ int mpccbf_build_neighbors(mpccbf_ctx* c, const double* states, int32_t num_stat
     const int rc = launch_neighbors(states, num_states, first, num_agents, k, radius, row_ptr, col,
                                     c->scratch.p, c->scratch.bytes, (hipStream_t)stream);
     if (rc != 0) return fail(MPCCBF_ERR_HIP, std::string("neighbour kernels: ") + hipGetErrorString((hipError_t)rc));
-    return MPCCBF_OK;
-}
-
-}  // extern "C"
-
-
-// ---------------------------------------------------------------------------------------------
-// Closed-loop stepping + RCCL exchange
-// ---------------------------------------------------------------------------------------------
-// In-process communicator group (mpccbf_comm_create_local): the ranks are host threads of one
-// process on one device; the per-step all-gather becomes device copies between their state
-// tables, ordered by one event per rank and step and a host barrier, so mpccbf_run_steps runs its
-// N-rank data flow (own block written by the IMPC kernel, exchange, the other blocks inserted
-// into the next neighbour table) on a single GPU.
-struct LocalGroup {
-    int nranks = 0;
-    std::mutex m;
-    std::condition_variable cv;
-    int arrived = 0;
-    long long gen = 0;
-    std::vector<double*> table[2];     // [step & 1][rank]: the table that rank wrote this step
-    std::vector<hipEvent_t> ev[2];     // [step & 1][rank]: that rank's IMPC kernel of the step done
-    // (double-buffered by step parity: a rank rewrites slot s & 1 only after the barrier of step
-    // s + 1, which every peer reaches after enqueueing its step-s copies)
-    std::vector<int> nsteps;           // [rank]: num_steps of the current mpccbf_run_steps call
-    bool aborted = false;              // a rank left early: every barrier fails from then on
-    // false: a rank aborted (the group cannot be used again; destroy and recreate it)
-    bool barrier() {
-        std::unique_lock<std::mutex> lk(m);
-        if (aborted) return false;
-        const long long g = gen;
-        if (++arrived == nranks) {
-            arrived = 0;
-            gen++;
-            cv.notify_all();
-            return true;
-        }
-        cv.wait(lk, [&] { return gen != g || aborted; });
-        return gen != g;
-    }
-    void abort() {
-        std::lock_guard<std::mutex> lk(m);
-        aborted = true;
-        cv.notify_all();
-    }
-};
-
-// Aborts the rank's in-process group when mpccbf_run_steps leaves before its last barrier, so the
-// peers' barriers return an error instead of waiting forever.
-struct GroupAbortGuard {
-    LocalGroup* g = nullptr;
-    ~GroupAbortGuard() {
-        if (g) g->abort();
-    }
-};
-
-struct mpccbf_comm {
-    ncclComm_t nccl = nullptr;
-    int nranks = 1, rank = 0, device = 0;
-    std::shared_ptr<LocalGroup> local;  // set: in-process group (no RCCL)
-};
-
-extern "C" {
-
-int mpccbf_comm_unique_id(char id_out[MPCCBF_COMM_ID_BYTES]) {
-    if (!id_out) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    static_assert(sizeof(ncclUniqueId) == MPCCBF_COMM_ID_BYTES, "ncclUniqueId size");
-    ncclUniqueId id;
-    const ncclResult_t r = ncclGetUniqueId(&id);
-    if (r != ncclSuccess) return fail(MPCCBF_ERR_HIP, std::string("ncclGetUniqueId: ") + ncclGetErrorString(r));
-    std::memcpy(id_out, &id, sizeof(id));
-    return MPCCBF_OK;
-}
-
-int mpccbf_comm_create(const char id[MPCCBF_COMM_ID_BYTES], int32_t nranks, int32_t rank, int32_t device,
-                       mpccbf_comm** out) {
-    if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "bad communicator arguments");
-    *out = nullptr;
-    HIP_TRY(hipSetDevice(device));
-    ncclUniqueId uid;
-    std::memcpy(&uid, id, sizeof(uid));
-    mpccbf_comm* cm = new mpccbf_comm();
-    cm->nranks = nranks;
-    cm->rank = rank;
-    cm->device = device;
-    const ncclResult_t r = ncclCommInitRank(&cm->nccl, nranks, uid, rank);
-    if (r != ncclSuccess) {
-        delete cm;
-        return fail(MPCCBF_ERR_HIP, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-    }
-    *out = cm;
-    return MPCCBF_OK;
-}
-
-int mpccbf_comm_create_local(int32_t nranks, int32_t device, mpccbf_comm** out) {
-    if (!out || nranks < 1) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "bad communicator arguments");
-    HIP_TRY(hipSetDevice(device));
-    auto g = std::make_shared<LocalGroup>();
-    g->nranks = nranks;
-    for (int p = 0; p < 2; p++) {
-        g->table[p].assign(nranks, nullptr);
-        g->ev[p].assign(nranks, nullptr);
-        for (int r = 0; r < nranks; r++) HIP_TRY(hipEventCreateWithFlags(&g->ev[p][r], hipEventDisableTiming));
-    }
-    g->nsteps.assign(nranks, 0);
-    for (int r = 0; r < nranks; r++) {
-        out[r] = new mpccbf_comm();
-        out[r]->nranks = nranks;
-        out[r]->rank = r;
-        out[r]->device = device;
-        out[r]->local = g;
-    }
-    return MPCCBF_OK;
-}
-
-void mpccbf_comm_destroy(mpccbf_comm* cm) {
-    if (!cm) return;
-    if (cm->nccl) (void)ncclCommDestroy(cm->nccl);
-    if (cm->local && cm->local.use_count() == 1)
-        for (int p = 0; p < 2; p++)
-            for (hipEvent_t e : cm->local->ev[p]) (void)hipEventDestroy(e);
-    delete cm;
-}
-
-int mpccbf_run_steps(mpccbf_ctx* c, const mpccbf_batch* b, mpccbf_run* r, void* stream_) {
-    if (!c || !b || !r) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    // (before the group's first barrier: a refused rank never joins it)
-    if (c->mon.on && r->comm && r->comm->nranks > 1)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "monitor: a communicator of more than one rank is not supported");
-    // in-process group: any return before the last step's barrier aborts the group (the peers
-    // get an error), and every rank must run the same number of steps
-    LocalGroup* lg = (r->comm && r->comm->nranks > 1 && r->comm->local) ? r->comm->local.get() : nullptr;
-    GroupAbortGuard guard{lg};
-    if (lg) {
-        {
-            std::lock_guard<std::mutex> lk(lg->m);
-            lg->nsteps[r->comm->rank] = r->num_steps;
-        }
-        if (!lg->barrier()) return fail(MPCCBF_ERR_HIP, "run: a rank of the in-process group aborted");
-        bool same = true;
-        {
-            std::lock_guard<std::mutex> lk(lg->m);
-            for (int v : lg->nsteps) same = same && v == r->num_steps;
-        }
-        // (every rank reads the counts before any rank can overwrite them at its next call's
-        // entry: that write follows this call's step barriers, or the abort below)
-        if (!same) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: ranks of the in-process group differ in num_steps");
-        if (r->num_steps == 0) {
-            c->grid.rot.no_rotation();
-            if (!lg->barrier()) return fail(MPCCBF_ERR_HIP, "run: a rank of the in-process group aborted");
-            guard.g = nullptr;
-            return MPCCBF_OK;
-        }
-    }
-    if (r->num_steps < 0 || !r->states_alt || !b->states)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: num_steps < 0 or missing state tables");
-    const int first = b->agent_first, count = b->num_agents, ns = b->num_states;
-    if (first < 0 || count < 0 || first + count > ns) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "agent range outside states");
-    if (r->comm && (ns != r->comm->nranks * count || first != r->comm->rank * count))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: ranks must own equal contiguous agent blocks");
-    {
-        const std::string est_err = fov_estimates_solve_error(c->est.on, false, r->comm ? r->comm->nranks : 1);
-        if (!est_err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, est_err);
-    }
-    if (r->num_steps > 0) {
-        const int mrc = monitor_step_check(c, b);
-        if (mrc != MPCCBF_OK) return mrc;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool timing = r->step_ms || r->solve_ms;
-    const int kcw = mpccbf_impc_launch_waves(c, count);  // (pairs per step)
-    if (r->kernel_clock && r->kernel_clock_waves < kcw)
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "run: kernel_clock_waves < mpccbf_impc_launch_waves (" +
-                                                     std::to_string(kcw) + ")");
-    if (r->kernel_clock && r->num_steps > 0)
-        HIP_TRY(hipMemsetAsync(r->kernel_clock, 0,
-                               2 * sizeof(uint64_t) * (size_t)r->kernel_clock_waves * (size_t)r->num_steps, stream));
-    const int need = 3 * std::max(r->num_steps, r->reserve_steps) + 1;
-    while ((int)c->events.size() < need) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->events.push_back(e);
-    }
-    double* tables[2] = {const_cast<double*>(b->states), r->states_alt};
-    const size_t per_log = (size_t)count * c->p.impc_iter;
-    mpccbf_batch sb = *b;
-    hipEvent_t* ev = c->events.data();
-    if (timing) HIP_TRY(hipEventRecord(ev[0], stream));
-    // grid mode: the rotation of the previous call continued, or neighbour table 0 from the initial
-    // states and table 1 zeroed for step 0's inserts (each IMPC launch zeroes the table two steps
-    // ahead). Only a grid-mode call that runs at least one step leaves a rotation to continue.
-    const bool gtab = b->nb_row_ptr == nullptr && count > 0 && r->num_steps > 0;
-    GridTables& gt = c->grid;
-    if (!gtab) gt.rot.no_rotation();
-    if (gtab) {
-        if (b->knn_k < 1 || !(b->knn_radius > 0))
-            return fail(MPCCBF_ERR_INVALID_ARGUMENT, "grid neighbours need knn_k >= 1 and knn_radius > 0");
-        int rc = gt.carve(ns);
-        if (rc != MPCCBF_OK) return rc;
-        const GridQuery q{b->states, ns, first, count, b->knn_k, b->knn_radius};
-        if (gt.rot.run_started(q, r->continue_tables != 0) < 0 &&
-            (rc = gt.rebuild(b->states, ns, b->knn_radius, true, stream)) != MPCCBF_OK)
-            return rc;
-    }
-    for (int s = 0; s < r->num_steps; s++) {
-        double* cur = tables[s & 1];
-        double* nxt = tables[(s & 1) ^ 1];
-        sb.states = cur;
-        sb.next_states = nxt + (size_t)first * 6;
-        sb.step_index = b->step_index + s;
-        if (r->status_log) sb.status = r->status_log + (size_t)s * per_log;
-        if (r->iters_log) sb.iters = r->iters_log + (size_t)s * per_log;
-        if (!r->comm) {  // rows this batch does not solve (static agents) carry over
-            if (first > 0)
-                HIP_TRY(hipMemcpyAsync(nxt, cur, (size_t)first * 6 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            const int tail = ns - first - count;
-            if (tail > 0)
-                HIP_TRY(hipMemcpyAsync(nxt + (size_t)(first + count) * 6, cur + (size_t)(first + count) * 6,
-                                       (size_t)tail * 6 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        }
-        // the attached filter's step against the table this step reads, ahead of the IMPC launch:
-        // mpccbf_pf_step over the batch's lists (pairs beyond the attached rows are skipped)
-        if (c->est.on && c->est.e.pf && b->nb_row_ptr && count > 0) {
-            const auto& e = c->est.e;
-            mpccbf_pf_batch pb;
-            std::memset(&pb, 0, sizeof(pb));
-            pb.num_states = ns;
-            pb.states = cur;
-            pb.agent_first = first;
-            pb.num_agents = count;
-            pb.nb_row_ptr = b->nb_row_ptr;
-            pb.nb_col = b->nb_col;
-            pb.num_pairs = e.num_pairs;  // (blocks; past the lists' end they leave at once)
-            pb.particles = e.particles;
-            pb.weights = e.weights;
-            pb.est_xy = e.est_xy;
-            pb.est_cov = e.est_cov;
-            pb.flags = e.flags;
-            pb.step_index = b->step_index + s;
-            const int prc = pf_enqueue(e.pf, &pb, c->device, stream, false, e.num_pairs);
-            if (prc != MPCCBF_OK) return prc;
-        }
-        const bool tk = r->solve_ms && (r->solve_stride <= 1 || s % r->solve_stride == 0);
-        const int rc = impc_enqueue(c, &sb, stream, tk ? ev[3 * s + 1] : nullptr, tk ? ev[3 * s + 2] : nullptr,
-                                    c->dev, c->store, gtab ? s : -1,
-                                    r->kernel_clock ? (unsigned long long*)r->kernel_clock +
-                                                          2 * (size_t)r->kernel_clock_waves * s
-                                                    : nullptr);
-        if (rc != MPCCBF_OK) return rc;
-        // (a single rank: the table of the next step is complete behind the IMPC launch)
-        const int mrc = monitor_after_step(c, &sb, stream);
-        if (mrc != MPCCBF_OK) return mrc;
-        if (r->comm && r->comm->nranks > 1 && r->comm->local) {
-            // in-process group: every rank's block of this step copied into this rank's table
-            LocalGroup& g = *r->comm->local;
-            const int me = r->comm->rank;
-            g.table[s & 1][me] = nxt;
-            HIP_TRY(hipEventRecord(g.ev[s & 1][me], stream));
-            if (!g.barrier()) return fail(MPCCBF_ERR_HIP, "run: a rank of the in-process group aborted");
-            for (int p = 0; p < g.nranks; p++) {
-                if (p == me) continue;
-                HIP_TRY(hipStreamWaitEvent(stream, g.ev[s & 1][p], 0));
-                HIP_TRY(hipMemcpyAsync(nxt + (size_t)p * count * 6, g.table[s & 1][p] + (size_t)p * count * 6,
-                                       (size_t)count * 6 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            }
-        } else if (r->comm && r->comm->nranks > 1) {
-            const ncclResult_t nr = ncclAllGather(nxt + (size_t)first * 6, nxt, (size_t)count * 6, ncclDouble,
-                                                  r->comm->nccl, stream);
-            if (nr != ncclSuccess) return fail(MPCCBF_ERR_HIP, std::string("ncclAllGather: ") + ncclGetErrorString(nr));
-        }
-        // the rows the kernel did not insert (static rows / the other ranks' rows) join the table
-        // of the next step
-        if (gtab && count < ns) {
-            const int t = gt.rot.step(s).fill;
-            HIP_TRY(launch_grid_insert(nxt, ns, first, first + count, b->knn_radius, gt.cnt[t], gt.slots[t],
-                                       gt.sst[t], stream));
-        }
-        if (r->step_ms || (timing && s == r->num_steps - 1)) HIP_TRY(hipEventRecord(ev[3 * s + 3], stream));
-    }
-    guard.g = nullptr;  // every barrier of the call passed: the peers no longer wait on this rank
-    r->final_table = r->num_steps & 1;
-    // where a continuing call picks the rotation up (mpccbf_run::continue_tables)
-    if (gtab) gt.rot.run_finished(tables[r->num_steps & 1], r->num_steps);
-    if (timing && r->num_steps > 0) {
-        HIP_TRY(hipEventSynchronize(ev[3 * (r->num_steps - 1) + 3]));
-        for (int s = 0; s < r->num_steps; s++) {
-            float ms = 0.f;
-            if (r->step_ms) {
-                HIP_TRY(hipEventElapsedTime(&ms, ev[s == 0 ? 0 : 3 * (s - 1) + 3], ev[3 * s + 3]));
-                r->step_ms[s] = ms;
-            }
-            if (r->solve_ms) {
-                if (r->solve_stride <= 1 || s % r->solve_stride == 0) {
-                    HIP_TRY(hipEventElapsedTime(&ms, ev[3 * s + 1], ev[3 * s + 2]));
-                    r->solve_ms[s] = ms;
-                } else {
-                    r->solve_ms[s] = -1.f;
-                }
-            }
-        }
-    }
     return MPCCBF_OK;
 }
 

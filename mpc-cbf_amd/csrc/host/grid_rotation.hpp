@@ -1,6 +1,6 @@
 // grid_rotation.hpp — which of grid mode's three neighbour tables a step reads, fills and zeroes,
 // and what one mpccbf_run_steps call leaves for the next to continue (mpccbf_run::continue_tables).
-// Decisions only: no HIP call, no allocation. The owner of the tables' buffer (capi.hip, GridTables)
+// Decisions only: no HIP call, no allocation. The owner of the tables' buffer (capi_ctx.hpp, GridTables)
 // makes the device calls these decisions ask for; tools/host_state_check.cpp drives the same class
 // against a model of the tables' contents (tests/test_host_state.py).
 //

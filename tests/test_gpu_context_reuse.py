@@ -11,7 +11,8 @@ of the same call on a fresh one:
 (b) the FoV kernels through a continuation (3 + 4 + 5 steps == 12 steps);
 (c) seeded call sequences on one context == every call alone on a fresh context, bit for bit;
 (d) agent counts at the tail of a wave / block against the oracle, rows past num_agents untouched;
-(e) a PreparedRun's timing arrays survive its next call.
+(e) a PreparedRun's timing arrays survive its next call;
+(f) solve_stride times the solves it names, and timing of any kind changes no result.
 
 Bit equality is the bar in (a)-(c): both sides run the same kernel, launch size and inputs, every
 agent is solved independently of the deferral queue's order, and the suite already holds the
@@ -438,3 +439,46 @@ def test_prepared_run_timings_survive_the_next_call(mpclib):
         assert not np.shares_memory(r1[k], r2[k]), k
         np.testing.assert_array_equal(r1[k], kept[k], err_msg=k)
         assert np.all(r2[k] > 0), k
+
+
+# ---- (f) solve_stride --------------------------------------------------------------------------
+
+def _timed_run(mpclib, torch, **timing):
+    """5 grid steps of the base collision config at 64 agents on a fresh context; the call's
+    result, and the final table, the status log and x on the host."""
+    cfg = swarm.config(15)
+    states, targets = swarm.lattice_swarm(64, seed=6)
+    states[:, :2] *= 0.6
+    dev = torch.device("cuda", 0)
+    ctx = mpclib.Context(cfg)
+    out = ctx.alloc_outputs(64)
+    a = torch.tensor(states, device=dev)
+    log = torch.full((5, 64, 2), -7, dtype=torch.int32, device=dev)
+    r = ctx.run_steps(a, torch.empty_like(a), 5, targets=torch.tensor(targets, device=dev), knn_k=K,
+                      knn_radius=RADIUS, x=out["x"], status_log=log, **timing)
+    torch.cuda.synchronize()
+    return r, (r["final"].cpu().numpy(), log.cpu().numpy(), out["x"].cpu().numpy())
+
+
+def test_solve_stride_times_every_other_solve_and_changes_no_result(mpclib):
+    """mpccbf_run::solve_stride = 2 over 5 steps: step_ms has its 5 positive entries, solve_ms the
+    3 of steps 0, 2 and 4 (the untimed steps' -1 dropped), each positive and no longer than its
+    step (the margin of test_run_steps_matches_step_by_step); solve_stride = 1 times all 5. Which
+    events a call records changes nothing it computes: the final table, the status log and x of
+    both timed runs equal those of an untimed run, bit for bit."""
+    torch = _torch()
+    _, plain = _timed_run(mpclib, torch, timing=False)
+    assert not np.any(plain[1] == -7)
+    every, got1 = _timed_run(mpclib, torch, timing=True, solve_stride=1)
+    other, got2 = _timed_run(mpclib, torch, timing=True, solve_stride=2)
+    print(f"solve_stride 1: step_ms {every['step_ms']} solve_ms {every['solve_ms']}\n"
+          f"solve_stride 2: step_ms {other['step_ms']} solve_ms {other['solve_ms']}")
+    assert every["step_ms"].shape == (5,) and every["solve_ms"].shape == (5,)
+    assert np.all(every["step_ms"] > 0) and np.all(every["solve_ms"] > 0)
+    assert np.all(every["solve_ms"] <= every["step_ms"] + 1e-3)
+    assert other["step_ms"].shape == (5,) and np.all(other["step_ms"] > 0)
+    assert other["solve_ms"].shape == (3,) and np.all(other["solve_ms"] > 0)
+    assert np.all(other["solve_ms"] <= other["step_ms"][[0, 2, 4]] + 1e-3)
+    for got in (got1, got2):
+        for g, p, name in zip(got, plain, ("final table", "status log", "x")):
+            np.testing.assert_array_equal(g, p, err_msg=name)

@@ -3,9 +3,9 @@
 // to a model of what the device buffers hold. Plain C++: no HIP, no library. Built by the Makefile
 // as build/host_state_check and run by tests/test_host_state.py.
 //
-// The driver below makes the calls of capi.hip (impc_enqueue, mpccbf_run_steps, GridTables::carve /
-// rebuild) on GridRotation and DeferQueues in capi.hip's order, and where capi.hip enqueues device
-// work it applies that work's effect to the model:
+// The driver below makes the calls of capi.hip (impc_enqueue), capi_run.hip (mpccbf_run_steps) and
+// capi_ctx.hpp (GridTables::carve / rebuild) on GridRotation and DeferQueues in their order, and
+// where they enqueue device work it applies that work's effect to the model:
 //   a neighbour table holds   ZERO | COPY of state version v | DIRTY | GONE (reallocated, or never there)
 //   a deferral queue's header ZERO | DIRTY | GONE
 //   a state table holds a version; every kernel that writes one, and every caller that may have,
@@ -35,7 +35,7 @@ struct Table {
     int ver = 0;
 };
 
-// the model's table size (capi.hip: grid_table_bytes; any function that grows with the power of
+// the model's table size (capi_ctx.hpp: grid_table_bytes; any function that grows with the power of
 // two >= num_states, from 1024 buckets, serves)
 unsigned table_size(int ns) {
     unsigned T = 1024;
@@ -86,7 +86,7 @@ void check(bool ok, const char* what) {
 
 // One context and the device memory behind it
 struct World {
-    // ---- what capi.hip holds ----
+    // ---- what the context holds ----
     GridRotation rot;
     DeferQueues queues;
     size_t grid_bytes = 0;  // GridTables::buf.bytes

@@ -832,6 +832,76 @@ int mpccbf_connectivity_control_solve(const mpccbf_connectivity_control_params* 
                                       const mpccbf_connectivity_control_batch* b, int32_t device,
                                       void* hip_stream);
 
+/* ---- Formation-control rollouts in the example's order (feature macro; MPCCBF_ABI_VERSION is
+ * unchanged: no struct changed layout) ---------------------------------------------------------
+ *
+ * The closed loop of cbf/examples/connectivity/CBFFormationControl_example.cpp:136-187 for a batch of
+ * independent teams (<= 16 robots each), one wavefront per team, the whole loop on the device. Per
+ * step, robot by robot in index order (robots before it have already moved): the critically damped
+ * spring control toward its target (Controls.h:18-27, spring_constant; the example's 0.5), the
+ * controller of mpccbf_connectivity_control_solve on the team's table as it stands (lambda2 is
+ * recomputed at every robot's turn), zero control unless OPTIMAL (:168-172), the double integrator
+ * (pos += Ts vel + Ts^2 u / 2, vel += Ts u; no yaw wrap) and the state noise pos_std / vel_std times
+ * normal_sample(team_seed[t], absolute step, robot's index in its team, component), a pure function
+ * of those four, so a team's run does not depend on its place in the batch or on how the steps are
+ * split over calls. After the last robot of step s the table is sample step_first + s.
+ *
+ * Records (optional, per decision, [num_steps][robots] rows in the order of `states`, robots =
+ * team_ptr[num_teams]): trace (the table's rows after the step), cbf_u (the control applied: zero
+ * where the solve failed), desired_u, status, lambda2 (what that decision saw), iters.
+ * Summary (optional, in/out so that calls chain; the caller initialises -1 / +inf / 0), scored as
+ * experiments/python/metrics/collision_check.py scores a states.json: arrival_sample = the first
+ * sample with the robot within goal_radius of its target (planar norm, <=); first_collision =
+ * (sample, i, j) of the first colliding pair (i < j indices in the team) under the script's box test
+ * on shape_half (:11-20, 28-39), earliest sample, then smallest i, then smallest j; min_d2 = the
+ * smallest squared planar distance of two robots of the team over the samples; fail_count = the
+ * decisions whose status was not OPTIMAL.
+ *
+ * The call is stateless and asynchronous: it enqueues ceil(num_steps / steps_per_launch) launches on
+ * the stream (steps_per_launch 0 = MPCCBF_FORMATION_STEPS_PER_LAUNCH) and returns; the results do not
+ * depend on the split. A team of more than 16 robots takes no step: every decision of it reports
+ * MPCCBF_ERROR with NaN cbf_u and lambda2, its states stay and its trace rows copy them, its
+ * fail_count counts them all. An empty team writes nothing.
+ * Refused with MPCCBF_ERR_INVALID_ARGUMENT on the host, before any device call: a NULL argument, the
+ * parameters mpccbf_connectivity_control_solve refuses, Ts not positive and finite, negative or
+ * non-finite spring_constant, pos_std, vel_std or goal_radius, shape_half not positive and finite,
+ * steps_per_launch < 0, negative num_teams, num_steps or step_first, step_first + num_steps beyond
+ * 2^31 - 1, and with teams and steps to run a NULL team_ptr, states, targets or team_seed.
+ * num_teams == 0 or num_steps == 0: MPCCBF_OK, nothing enqueued. */
+#define MPCCBF_HAS_FORMATION_ROLLOUT 1
+#define MPCCBF_FORMATION_STEPS_PER_LAUNCH 2
+typedef struct mpccbf_formation_params {
+    double Ts;
+    double spring_constant;
+    double pos_std, vel_std;
+    double shape_half[2];      /* the box's half extents as collision_check.py takes them */
+    double goal_radius;        /* as given (the script's default is 1.0); 0: only a robot on its target */
+    int32_t steps_per_launch;  /* 0 = MPCCBF_FORMATION_STEPS_PER_LAUNCH */
+} mpccbf_formation_params;
+
+typedef struct mpccbf_formation_batch {
+    int32_t num_teams;
+    const int32_t* team_ptr;    /* num_teams + 1 offsets into the robot rows */
+    double* states;             /* robots x 6, in/out: the table after the last step */
+    const double* targets;      /* robots x 3 */
+    const uint64_t* team_seed;  /* num_teams */
+    int64_t step_first;         /* absolute index of the first step (noise key, sample numbers) */
+    int32_t num_steps;
+    double* trace;              /* out, [num_steps][robots][6], or NULL */
+    double* cbf_u;              /* out, [num_steps][robots][3], or NULL */
+    double* desired_u;          /* out, [num_steps][robots][3], or NULL */
+    int32_t* status;            /* out, [num_steps][robots], or NULL */
+    double* lambda2;            /* out, [num_steps][robots], or NULL */
+    int32_t* iters;             /* out, [num_steps][robots], or NULL */
+    int32_t* arrival_sample;    /* in/out, robots (-1: not yet), or NULL */
+    int32_t* first_collision;   /* in/out, num_teams x 3 (sample, i, j; -1: none), or NULL */
+    double* min_d2;             /* in/out, num_teams (+inf), or NULL */
+    int32_t* fail_count;        /* in/out, num_teams, or NULL */
+} mpccbf_formation_batch;
+
+int mpccbf_formation_rollout(const mpccbf_connectivity_control_params* p, const mpccbf_formation_params* f,
+                             const mpccbf_formation_batch* b, int32_t device, void* hip_stream);
+
 /* Generic dense QP in the flattened CPLEX form (host pointers; synchronous):
  *   minimise  x^T H x + c^T x + c0        (H symmetric: sum_{i<=j} q_ij x_i x_j, CPLEX.cpp:122-147)
  *   s.t.      lo_r <= A_r x <= hi_r       (rows; lo == hi is an equality)

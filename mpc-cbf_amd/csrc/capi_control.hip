@@ -1,5 +1,6 @@
 // capi_control.hip — the C ABI's entry points that hold no context: the CBF-only controllers
-// (mpccbf_connectivity_control_solve, mpccbf_fov_rows_eval, mpccbf_fov_control_solve) and the FoV
+// (mpccbf_connectivity_control_solve, mpccbf_formation_rollout, mpccbf_fov_rows_eval,
+// mpccbf_fov_control_solve) and the FoV
 // particle filter (mpccbf_pf_init, mpccbf_pf_step) and the safety monitor (mpccbf_monitor_reset,
 // mpccbf_monitor_score). Each checks its arguments on the host, fills the kernel's argument struct
 // and enqueues its launches.
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "../../include/mpccbf.h"
+#include "host/formation_args.hpp"
 #include "host/fov_estimates.hpp"
 #include "host/hip_host.hpp"
 #include "kernels/cbf_control.hpp"
@@ -20,20 +22,33 @@
 
 using namespace mpccbf;
 
+// the per-robot QP's parameters with the defaults applied (both connectivity entry points)
+static ConnQpParams conn_qp_params(const mpccbf_connectivity_control_params& p) {
+    ConnQpParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.dmin = p.d_min;
+    q.dmax = p.d_max;
+    for (int d = 0; d < 3; d++) {
+        q.vmin[d] = p.v_min[d];
+        q.vmax[d] = p.v_max[d];
+    }
+    q.maxit = p.max_pdip_iters > 0 ? p.max_pdip_iters : 60;
+    q.tol = p.tolerance > 0.0 ? p.tolerance : 1e-9;
+    q.feas_tol = 1e-6;
+    q.slack_mode = p.slack_mode ? 1 : 0;
+    q.slack_cost = p.slack_cost;
+    q.slack_decay = p.slack_decay_rate;
+    return q;
+}
+
 extern "C" {
 
 int mpccbf_connectivity_control_solve(const mpccbf_connectivity_control_params* p,
                                       const mpccbf_connectivity_control_batch* b, int32_t device,
                                       void* stream) {
     if (!p || !b) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "null argument");
-    if (!(p->d_min > 0.0) || !(p->d_max > 0.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "d_min and d_max must be positive");
-    for (int d = 0; d < 3; d++)
-        if (!(p->v_min[d] <= p->v_max[d])) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "v_min must not exceed v_max");
-    if (p->slack_mode && !(p->slack_cost > 0.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack cost must be positive when slack_mode is enabled");
-    if (p->slack_mode && !(p->slack_decay_rate > 0.0 && p->slack_decay_rate <= 1.0))
-        return fail(MPCCBF_ERR_INVALID_ARGUMENT, "Slack decay rate must be in (0,1] when slack_mode is enabled");
+    const std::string perr = conn_control_params_error(*p);
+    if (!perr.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, perr);
     if (b->num_teams < 0) return fail(MPCCBF_ERR_INVALID_ARGUMENT, "num_teams < 0");
     if (b->num_teams == 0) return MPCCBF_OK;
     if (!b->team_ptr || !b->states || !b->desired_u || !b->u)
@@ -53,19 +68,56 @@ int mpccbf_connectivity_control_solve(const mpccbf_connectivity_control_params* 
     a.obj = b->obj;
     a.iters = b->iters;
     a.lambda2 = b->lambda2;
-    a.dmin = p->d_min;
-    a.dmax = p->d_max;
-    for (int d = 0; d < 3; d++) {
-        a.vmin[d] = p->v_min[d];
-        a.vmax[d] = p->v_max[d];
-    }
-    a.maxit = p->max_pdip_iters > 0 ? p->max_pdip_iters : 60;
-    a.tol = p->tolerance > 0.0 ? p->tolerance : 1e-9;
-    a.feas_tol = 1e-6;
-    a.slack_mode = p->slack_mode ? 1 : 0;
-    a.slack_cost = p->slack_cost;
-    a.slack_decay = p->slack_decay_rate;
+    a.qp = conn_qp_params(*p);
     HIP_TRY(launch_connectivity_control(a, (hipStream_t)stream));
+    return MPCCBF_OK;
+}
+
+int mpccbf_formation_rollout(const mpccbf_connectivity_control_params* p, const mpccbf_formation_params* f,
+                             const mpccbf_formation_batch* b, int32_t device, void* stream) {
+    const std::string err = formation_args_error(p, f, b);
+    if (!err.empty()) return fail(MPCCBF_ERR_INVALID_ARGUMENT, err);
+    if (b->num_teams == 0 || b->num_steps == 0) return MPCCBF_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MPCCBF_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    FormationArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.num_teams = b->num_teams;
+    a.team_ptr = b->team_ptr;
+    a.states = b->states;
+    a.targets = b->targets;
+    a.team_seed = b->team_seed;
+    a.trace = b->trace;
+    a.cbf_u = b->cbf_u;
+    a.desired_u = b->desired_u;
+    a.status = b->status;
+    a.lambda2 = b->lambda2;
+    a.iters = b->iters;
+    a.arrival_sample = b->arrival_sample;
+    a.first_collision = b->first_collision;
+    a.min_d2 = b->min_d2;
+    a.fail_count = b->fail_count;
+    a.qp = conn_qp_params(*p);
+    a.Ts = f->Ts;
+    a.spring = f->spring_constant;
+    a.pos_std = f->pos_std;
+    a.vel_std = f->vel_std;
+    a.half_x = f->shape_half[0];
+    a.half_y = f->shape_half[1];
+    a.goal_radius = f->goal_radius;
+    // the steps in launches of at most steps_per_launch on the one stream: each continues from the
+    // table and the summary the one before it left
+    const int32_t per = formation_steps_per_launch(*f);
+    for (int32_t k = 0;; k++) {
+        const FormationLaunch l = formation_launch(b->num_steps, per, k);
+        if (l.count == 0) break;
+        a.step_first = b->step_first + l.first;
+        a.record_first = l.first;
+        a.num_steps = l.count;
+        HIP_TRY(launch_formation_rollout(a, (hipStream_t)stream));
+    }
     return MPCCBF_OK;
 }
 

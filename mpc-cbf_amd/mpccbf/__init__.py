@@ -9,11 +9,13 @@ from ._lib import (  # noqa: F401
     dense_qp_solve, dense_qp_solve_batch, STATUS_NAMES, OPTIMAL, FEASIBLE, UNBOUNDED, INFEASIBLE, ERROR, UNKNOWN,
     INFEASIBLEORUNBOUNDED, Comm, comm_unique_id, fov_control_solve, fov_control_params,
     connectivity_control_solve, decode_active_sides, encode_active_side, audit_summary,
-    PfParams, PfBatch, pf_params, pf_init, pf_step,
+    PfParams, PfBatch, pf_params, pf_init, pf_step, formation_rollout,
 )
 from . import swarm  # noqa: F401
 from . import monitor  # noqa: F401
 from .monitor import SafetyMonitor  # noqa: F401
+from . import formation  # noqa: F401
+from .formation import FormationRollouts  # noqa: F401
 from .estimator import FovEstimator  # noqa: F401
 from .fov_control_sim import FovControlLoop  # noqa: F401
 from .fov_impc_sim import FovImpcLoop  # noqa: F401

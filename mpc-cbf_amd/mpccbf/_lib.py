@@ -27,6 +27,7 @@ EXPORTED = [
     "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step", "mpccbf_launch_form",
     "mpccbf_host_launch_form", "mpccbf_set_fov_estimates", "mpccbf_monitor_scratch_bytes",
     "mpccbf_monitor_table_size", "mpccbf_monitor_reset", "mpccbf_monitor_score", "mpccbf_set_monitor",
+    "mpccbf_formation_rollout",
 ]
 
 # ImpcKernel ids (csrc/kernels/launch_plan.hpp) of the 16-lane main launch: generic and loop form
@@ -293,6 +294,9 @@ def load():
     for f in ("mpccbf_pf_init", "mpccbf_pf_step"):
         # (PfParams / PfBatch are defined below; resolved at call time)
         getattr(L, f).argtypes = [C.POINTER(PfParams), C.POINTER(PfBatch), C.c_int32, vp]
+    if hasattr(L, "mpccbf_formation_rollout"):  # (MPCCBF_LIB may name a library from before the rollouts)
+        L.mpccbf_formation_rollout.argtypes = [C.POINTER(ConnControlParams), C.POINTER(FormationParams),
+                                               C.POINTER(FormationBatch), C.c_int32, vp]
     _lib = L
     return L
 
@@ -971,11 +975,9 @@ class ConnControlBatch(C.Structure):
                 ("obj", C.c_void_p), ("iters", C.c_void_p), ("lambda2", C.c_void_p)]
 
 
-def connectivity_control_solve(cfg: dict, team_ptr, states, desired_u, u, status=None, obj=None,
-                               iters=None, lambda2=None, device: int = 0, stream=None):
-    """Batched ConnectivityControl::optimize (mpccbf_connectivity_control_solve) for teams of
-    robots (team t = rows team_ptr[t] .. team_ptr[t+1]-1 of states / desired_u). cfg keys: d_min,
-    d_max, v_min, v_max, control_slack_mode, slack_cost, slack_decay_rate."""
+def conn_control_params(cfg: dict) -> ConnControlParams:
+    """The connectivity controller's parameters from a config dict: d_min, d_max, v_min, v_max,
+    control_slack_mode, slack_cost, slack_decay_rate."""
     p = ConnControlParams()
     p.d_min, p.d_max = cfg["d_min"], cfg["d_max"]
     for d in range(3):
@@ -983,11 +985,67 @@ def connectivity_control_solve(cfg: dict, team_ptr, states, desired_u, u, status
     p.slack_mode = int(cfg.get("control_slack_mode", 0))
     p.slack_cost = cfg.get("slack_cost", 0.0)
     p.slack_decay_rate = cfg.get("slack_decay_rate", 1.0)
+    return p
+
+
+def connectivity_control_solve(cfg: dict, team_ptr, states, desired_u, u, status=None, obj=None,
+                               iters=None, lambda2=None, device: int = 0, stream=None):
+    """Batched ConnectivityControl::optimize (mpccbf_connectivity_control_solve) for teams of
+    robots (team t = rows team_ptr[t] .. team_ptr[t+1]-1 of states / desired_u). cfg keys: d_min,
+    d_max, v_min, v_max, control_slack_mode, slack_cost, slack_decay_rate."""
+    p = conn_control_params(cfg)
     b = ConnControlBatch(num_teams=team_ptr.shape[0] - 1, team_ptr=_ptr(team_ptr),
                          states=_ptr(states), desired_u=_ptr(desired_u), u=_ptr(u),
                          status=_ptr(status), obj=_ptr(obj), iters=_ptr(iters),
                          lambda2=_ptr(lambda2))
     _check(load().mpccbf_connectivity_control_solve(C.byref(p), C.byref(b), device, _stream(stream)))
+
+
+FORMATION_STEPS_PER_LAUNCH = 2  # MPCCBF_FORMATION_STEPS_PER_LAUNCH
+
+
+class FormationParams(C.Structure):
+    _fields_ = [("Ts", C.c_double), ("spring_constant", C.c_double), ("pos_std", C.c_double),
+                ("vel_std", C.c_double), ("shape_half", C.c_double * 2), ("goal_radius", C.c_double),
+                ("steps_per_launch", C.c_int32)]
+
+
+class FormationBatch(C.Structure):
+    _fields_ = [("num_teams", C.c_int32), ("team_ptr", C.c_void_p), ("states", C.c_void_p),
+                ("targets", C.c_void_p), ("team_seed", C.c_void_p), ("step_first", C.c_int64),
+                ("num_steps", C.c_int32), ("trace", C.c_void_p), ("cbf_u", C.c_void_p),
+                ("desired_u", C.c_void_p), ("status", C.c_void_p), ("lambda2", C.c_void_p),
+                ("iters", C.c_void_p), ("arrival_sample", C.c_void_p), ("first_collision", C.c_void_p),
+                ("min_d2", C.c_void_p), ("fail_count", C.c_void_p)]
+
+
+def formation_rollout(cfg: dict, team_ptr, states, targets, team_seed, num_steps: int, step_first: int = 0, *,
+                      Ts: float, spring_constant: float = 0.5, pos_std: float = 0.0, vel_std: float = 0.0,
+                      shape_half=(0.2, 0.2), goal_radius: float = 1.0, steps_per_launch: int = 0,
+                      trace=None, cbf_u=None, desired_u=None, status=None, lambda2=None, iters=None,
+                      arrival_sample=None, first_collision=None, min_d2=None, fail_count=None,
+                      device: int = 0, stream=None):
+    """The formation-control example's closed loop for a batch of teams on the device
+    (mpccbf_formation_rollout): num_steps steps from step_first, robots in index order. Device
+    tensors: team_ptr (int32, teams + 1), states (robots x 6, in/out), targets (robots x 3),
+    team_seed (int64 holding the uint64 seeds' bits, teams); the optional records
+    [num_steps][robots][.] and the in/out summary (arrival_sample int32 robots, first_collision int32
+    teams x 3, min_d2 float64 teams, fail_count int32 teams). cfg: the keys of
+    connectivity_control_solve."""
+    p = conn_control_params(cfg)
+    f = FormationParams(Ts=Ts, spring_constant=spring_constant, pos_std=pos_std, vel_std=vel_std,
+                        goal_radius=goal_radius, steps_per_launch=int(steps_per_launch))
+    f.shape_half[0], f.shape_half[1] = float(shape_half[0]), float(shape_half[1])
+    b = FormationBatch(num_teams=team_ptr.shape[0] - 1, team_ptr=_ptr(team_ptr), states=_ptr(states),
+                       targets=_ptr(targets), team_seed=_ptr(team_seed), step_first=int(step_first),
+                       num_steps=int(num_steps), trace=_ptr(trace), cbf_u=_ptr(cbf_u),
+                       desired_u=_ptr(desired_u), status=_ptr(status), lambda2=_ptr(lambda2),
+                       iters=_ptr(iters), arrival_sample=_ptr(arrival_sample),
+                       first_collision=_ptr(first_collision), min_d2=_ptr(min_d2), fail_count=_ptr(fail_count))
+    L = load()
+    if not hasattr(L, "mpccbf_formation_rollout"):
+        raise MpccbfError(f"{LIB_PATH} has no mpccbf_formation_rollout (a library from before the rollouts)")
+    _check(L.mpccbf_formation_rollout(C.byref(p), C.byref(f), C.byref(b), int(device), _stream(stream)))
 
 
 def comm_unique_id() -> bytes:

@@ -23,7 +23,7 @@ import functools
 
 import numpy as np
 
-from test_dense_qp import INF, _random_qp
+INF = np.finfo(np.float64).max  # numeric_limits<double>::max() as qpcpp::Problem uses it
 
 # the host's constants (test_dense_route_inputs.py checks them against the limits dense_route_check prints)
 WR = 3
@@ -37,6 +37,34 @@ SLICE_COUNT = 1024   # count >= SLICE_COUNT: 4 slices
 EARLY_COUNT = 64     # count <= EARLY_COUNT: the early exit's host check
 STAGE_BYTES = 48 * 1024
 K_INF = 1e300
+
+
+def toy():
+    # min x^2 + y^2  s.t.  x + y >= 1   (CPLEXTest.cpp:34-47)
+    return dict(H=np.eye(2), c=np.zeros(2), A=np.array([[1.0, 1.0]]), lo=np.array([1.0]),
+                hi=np.array([INF]))
+
+
+def _random_qp(rng, n, me, mi, redundant=0, fixed=0):
+    """A strictly convex QP with me equalities (redundant copies appended), mi two-sided rows
+    and `fixed` fixed variables, feasible by construction around x0."""
+    M = rng.standard_normal((n, n))
+    H = M @ M.T / n + 0.1 * np.eye(n)
+    c = rng.standard_normal(n)
+    x0 = rng.standard_normal(n)
+    E = rng.standard_normal((me, n))
+    if redundant:
+        E = np.vstack([E, rng.standard_normal((redundant, me)) @ E])
+    G = rng.standard_normal((mi, n))
+    gx = G @ x0
+    A = np.vstack([E, G])
+    lo = np.concatenate([E @ x0, gx - rng.uniform(0.05, 1.0, mi)])
+    hi = np.concatenate([E @ x0, gx + rng.uniform(0.05, 1.0, mi)])
+    vlo = np.full(n, -INF)
+    vhi = np.full(n, INF)
+    for i in range(fixed):
+        vlo[i] = vhi[i] = x0[i]
+    return dict(H=H, c=c, A=A, lo=lo, hi=hi, vlo=vlo, vhi=vhi, c0=0.25)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -12,14 +12,9 @@ import os
 import numpy as np
 import pytest
 
-INF = np.finfo(np.float64).max  # numeric_limits<double>::max() as qpcpp::Problem uses it
+from dense_route_cases import INF, _random_qp, toy
+
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "golden_qps.npz")
-
-
-def toy():
-    # min x^2 + y^2  s.t.  x + y >= 1   (CPLEXTest.cpp:34-47)
-    return dict(H=np.eye(2), c=np.zeros(2), A=np.array([[1.0, 1.0]]), lo=np.array([1.0]),
-                hi=np.array([INF]))
 
 
 def test_one_scan_packer_matches_two_pass_form(tmp_path):
@@ -120,28 +115,6 @@ def test_dense_golden_mpc_qps(mpclib):
         ref = float(g[f"c{i}_obj"])
         assert abs(obj[i] - ref) <= 1e-4 * max(1.0, abs(ref)), (i, obj[i], ref)
         assert np.max(np.abs(xs[i] - g[f"c{i}_x"])) <= 1e-5
-
-
-def _random_qp(rng, n, me, mi, redundant=0, fixed=0):
-    """A strictly convex QP with me equalities (redundant copies appended), mi two-sided rows
-    and `fixed` fixed variables, feasible by construction around x0."""
-    M = rng.standard_normal((n, n))
-    H = M @ M.T / n + 0.1 * np.eye(n)
-    c = rng.standard_normal(n)
-    x0 = rng.standard_normal(n)
-    E = rng.standard_normal((me, n))
-    if redundant:
-        E = np.vstack([E, rng.standard_normal((redundant, me)) @ E])
-    G = rng.standard_normal((mi, n))
-    gx = G @ x0
-    A = np.vstack([E, G])
-    lo = np.concatenate([E @ x0, gx - rng.uniform(0.05, 1.0, mi)])
-    hi = np.concatenate([E @ x0, gx + rng.uniform(0.05, 1.0, mi)])
-    vlo = np.full(n, -INF)
-    vhi = np.full(n, INF)
-    for i in range(fixed):
-        vlo[i] = vhi[i] = x0[i]
-    return dict(H=H, c=c, A=A, lo=lo, hi=hi, vlo=vlo, vhi=vhi, c0=0.25)
 
 
 @pytest.mark.gpu

@@ -11,7 +11,7 @@ import pytest
 import exact_geometry_cases as X
 import oracle_lib as O
 from mpccbf import swarm
-from test_gpu_parity import OBJ_TOL, X_TOL
+from parity_rule import check_parity
 
 
 def _hist(rp):
@@ -190,9 +190,9 @@ def test_dependent_point_oracle_verdicts():
         for other in (X.unique_sorted(lst), X.collapsed(states, lst)):
             u = X.oracle_point(cfg, target, other)
             assert list(u["status"]) == [O.OPTIMAL, O.OPTIMAL]
-            for it in range(2):
-                assert abs(r["obj"][it] - u["obj"][it]) <= OBJ_TOL * max(1.0, abs(u["obj"][it])), (name, it)
-                assert np.max(np.abs(r["x"][it][:n] - u["x"][it][:n])) <= X_TOL, (name, it)
+            for k in (1, 2):  # the rule holds the last curve: over iteration 0 alone, then over both
+                got = dict(status=np.array([r["status"][:k]]), obj=np.array([r["obj"][:k]]), x=np.array([r["x"][k - 1][:n]]))
+                check_parity(got, [dict(status=u["status"][:k], obj=u["obj"][:k], x=u["x"][:k])], label=name)
         if name in want:
             np.testing.assert_allclose(r["obj"], want[name], atol=2e-6)
     # an active CBF row in iteration 0: without the neighbour the optimum is lower

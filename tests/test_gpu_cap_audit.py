@@ -21,13 +21,13 @@ import pytest
 import cap_audit_ref as R
 from mpccbf import swarm
 from mpccbf.sim import Simulator
-from test_gpu_parity import _torch
+from gpu_harness import require_gpu, same_bits, to_device
+from parity_rule import ROUTE_REL, check_routes_agree
 
 pytestmark = pytest.mark.gpu
 
 RADIUS = 6.0
 SEP16, WIDE = 4, 5
-REL = 1e-7
 OPTIMAL, INFEASIBLE = 0, 3
 
 
@@ -39,7 +39,7 @@ def _solve(mpclib, n, k=None, variant=0, csr=None, first=0, count=None, ctx=None
     """One IMPC step of agents first .. first + count - 1 of the n-agent scenario: grid mode with
     the k nearest (nb_out kept), or csr = (row_ptr, col) of the whole swarm. Returns the context,
     the device tensors and the keyword arguments audit_neighbors needs for that batch."""
-    torch = _torch()
+    torch = require_gpu()
     cfg, st, targets = R.scenario(n)
     if states is not None:
         st = states
@@ -58,8 +58,8 @@ def _solve(mpclib, n, k=None, variant=0, csr=None, first=0, count=None, ctx=None
         lists["nb_out"] = nb_out
     else:
         rp, col = csr
-        lists = dict(nb_row_ptr=torch.tensor(np.ascontiguousarray(rp[first:first + count + 1]), device=dev),
-                     nb_col=torch.tensor(col if len(col) else np.zeros(1, np.int32), device=dev))
+        lists = dict(nb_row_ptr=to_device(rp[first:first + count + 1]),
+                     nb_col=to_device(col))
         ctx.impc_solve(a, targets=tg, agent_first=first, num_agents=count, x=out["x"], status=out["status"],
                        obj=out["obj"], iters=out["iters"], **lists)
     torch.cuda.synchronize()
@@ -73,7 +73,7 @@ def _grid_audit(mpclib, n, k, variant=0):
     host arrays."""
     s = _solve(mpclib, n, k, variant)
     res = s["ctx"].audit_neighbors(s["states"], live_nb=True, x0=True, **s["akw"])
-    _torch().cuda.synchronize()
+    require_gpu().cuda.synchronize()
     r = {key: _np(v) for key, v in res.items()}
     r.update(status=_np(s["out"]["status"]), obj=_np(s["out"]["obj"]), x=_np(s["out"]["x"]),
              nb_out=_np(s["akw"]["nb_out"]), states=s["states_np"], cfg=s["cfg"], kernel=s["kernel"])
@@ -124,10 +124,6 @@ def _all_others(mpclib, variant):
     return dict(status=_np(s["out"]["status"]), obj=_np(s["out"]["obj"]), x=_np(s["out"]["x"]))
 
 
-def _rel(a, b):
-    return np.abs(a - b) / np.maximum(1.0, np.abs(b))
-
-
 @pytest.mark.parametrize("variant", [SEP16, WIDE])
 @pytest.mark.parametrize("k", [1, 2])
 def test_certificate_means_what_it_says(mpclib, k, variant):
@@ -144,20 +140,17 @@ def test_certificate_means_what_it_says(mpclib, k, variant):
     assert not np.any(bit1 & ~bit0)
     np.testing.assert_array_equal(st[bit0, 0], full["status"][bit0, 0])
     o = bit0 & (st[:, 0] == OPTIMAL)
-    e0 = _rel(obj[o, 0], full["obj"][o, 0])
+    check_routes_agree(obj[o, 0], full["obj"][o, 0], "certified agents: objective, iteration 0")
     np.testing.assert_array_equal(st[bit1], full["status"][bit1])
     o1 = bit1 & (st[:, 1] == OPTIMAL)
-    e1 = _rel(obj[o1, 1], full["obj"][o1, 1])
+    check_routes_agree(obj[o1, 1], full["obj"][o1, 1], "certified agents: objective, iteration 1")
     hasx = bit1 & (st == OPTIMAL).any(axis=1)
-    ex = _rel(g["x"][hasx], full["x"][hasx])
-    print(f"certified agents: objective rel err max {e0.max():.3e} (iteration 0), {e1.max():.3e} (iteration 1), "
-          f"x rel err max {ex.max():.3e}")
-    assert e0.max() <= REL and e1.max() <= REL and ex.max() <= REL
+    check_routes_agree(g["x"][hasx], full["x"][hasx], "certified agents: x")
     np.testing.assert_array_equal(np.isnan(g["x"][bit1]), np.isnan(full["x"][bit1]))
     # the flagged agents: the capped optimum breaks a row of the all-others QP, whose optimum is
     # therefore strictly more expensive (a relaxation's optimum that is infeasible for the full QP)
     fo, fs = full["obj"][viol0, 0], full["status"][viol0, 0]
-    worse = (fs != OPTIMAL) | ((fo - obj[viol0, 0]) > REL * np.maximum(1.0, np.abs(obj[viol0, 0])))
+    worse = (fs != OPTIMAL) | ((fo - obj[viol0, 0]) > ROUTE_REL * np.maximum(1.0, np.abs(obj[viol0, 0])))
     print(f"flagged agents: all-others iteration 0 not OPTIMAL on {np.count_nonzero(fs != OPTIMAL)}, smallest "
           f"relative objective increase {np.min(((fo - obj[viol0, 0]) / np.maximum(1.0, np.abs(obj[viol0, 0])))[fs == OPTIMAL], initial=np.inf):.3e}")
     assert worse.all(), np.nonzero(viol0)[0][~worse]
@@ -182,7 +175,7 @@ def test_complete_lists_are_never_flagged(mpclib):
 
 
 def test_csr_lists_and_a_partial_batch(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     g = _grid_audit(mpclib, 64, 1)
     rp, col = swarm.knn_csr(g["states"], 1, RADIUS)
     s = _solve(mpclib, 64, csr=(rp, col), first=16, count=32)
@@ -222,7 +215,7 @@ def test_csr_lists_and_a_partial_batch(mpclib):
 
 
 def test_audit_leaves_the_callers_data_alone(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     cfg, states, targets = R.scenario(64)
     dev = torch.device("cuda", 0)
     ctx = mpclib.Context(cfg)
@@ -244,9 +237,7 @@ def test_audit_leaves_the_callers_data_alone(mpclib):
                               knn_radius=RADIUS)
     torch.cuda.synchronize()
     assert np.count_nonzero(_np(res["counts"])[:, 1] > 0) >= 10
-    for k, v in keep.items():  # bit for bit (NaN patterns included)
-        got = _np(v)
-        assert got.tobytes() == before[k].tobytes(), k
+    same_bits(keep, before, what="after the audit")  # (NaN patterns included)
     # the audit of a solve with a store attached is the audit of the plain solve
     np.testing.assert_array_equal(_np(res["counts"]), _grid_audit(mpclib, 64, 1)["counts"])
 
@@ -274,7 +265,7 @@ def test_simulator_with_audit_reproduces_the_plain_run(mpclib):
 def test_continued_run_after_an_audit_equals_the_run_without(mpclib):
     """The audit's own launch ends a continue_tables rotation like any mpccbf_impc_solve: the next
     mpccbf_run_steps rebuilds its table, and its results are those of the run without the audit."""
-    torch = _torch()
+    torch = require_gpu()
     cfg, states, targets = R.scenario(64)
     dev = torch.device("cuda", 0)
     finals, logs = [], []
@@ -299,7 +290,7 @@ def test_continued_run_after_an_audit_equals_the_run_without(mpclib):
 
 
 def test_device_side_argument_and_capacity_errors(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     s = _solve(mpclib, 64, 1)
     ctx, akw = s["ctx"], s["akw"]
@@ -332,7 +323,7 @@ def test_device_side_argument_and_capacity_errors(mpclib):
 
 
 def test_simulator_rejects_what_the_audit_does_not_support(mpclib):
-    _torch()
+    require_gpu()
     cfg, states, targets = R.scenario(16)
     with pytest.raises(ValueError, match="jacobi"):
         Simulator(cfg, states, targets, audit=True, order="gauss_seidel")

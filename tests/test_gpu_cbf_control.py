@@ -10,18 +10,12 @@ import pytest
 
 import cbf_control_cases as Cs
 import oracle_lib as O
+from gpu_harness import require_gpu, to_device
 
 pytestmark = pytest.mark.gpu
 
 POISON = -12345.678
 LEGAL = (O.OPTIMAL, O.INFEASIBLE, O.UNKNOWN)
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
 
 
 def _fov_solve(torch, mpclib, cfg, agents, outputs=True, use_cov=True):
@@ -30,7 +24,7 @@ def _fov_solve(torch, mpclib, cfg, agents, outputs=True, use_cov=True):
     dev = torch.device("cuda", 0)
     states, desired, rp, nb, cov = Cs.fov_batch(agents)
     n = len(agents)
-    t = lambda v, dt=torch.float64: torch.tensor(np.ascontiguousarray(v), dtype=dt, device=dev)  # noqa: E731
+    t = lambda v, dt=torch.float64: to_device(v, dt)  # noqa: E731
     u = torch.full((n + 1, 3), POISON, dtype=torch.float64, device=dev)
     status = torch.full((n + 1,), -77, dtype=torch.int32, device=dev)
     obj = torch.full((n + 1,), POISON, dtype=torch.float64, device=dev)
@@ -101,7 +95,7 @@ def test_fov_plain_cases(mpclib, fov):
     (ERROR, NaN u and objective, 0 iterations), fov 60 / 180 / 240 / 360 degrees at headings +-pi
     and 7.0, a neighbour at the ego position, velocity at and beyond v_max (INFEASIBLE).
     Measured on the MI355X: max |u - exact| 1.7e-10 (scaled), objective 2.6e-10 (relative)."""
-    torch = _torch()
+    torch = require_gpu()
     worst = dict(u=0.0, obj=0.0)
     names = [n for n, e in fov.items() if not e["case"]["cfg"].get("control_slack_mode")]
     seen = set()
@@ -121,7 +115,7 @@ def test_fov_batch_tails(mpclib, fov, n):
     it alone reports ERROR, and the others equal, bit for bit, the same agents solved without it.
     A second launch without status / obj / iters writes the same u.
     Measured on the MI355X: max |u - exact| 9.4e-11 (scaled), objective 7.2e-11 (relative)."""
-    torch = _torch()
+    torch = require_gpu()
     err = Cs.ERROR_SLOT if n == 17 else None
     pool = Cs.plain_pool(n, with_error=err)
     cfg = pool[0]["cfg"]
@@ -148,7 +142,7 @@ def test_fov_slack_cases(mpclib, fov):
     slacks.
     Measured on the MI355X: |obj - penalty(u)| 5.6e-12, penalty gap to the oracle's point 8.0e-10
     (both relative), |u - oracle| 3.0e-8 (scaled)."""
-    torch = _torch()
+    torch = require_gpu()
     worst = dict(u=0.0, obj=0.0, gap=0.0, hard=-np.inf)
     names = [n for n, e in fov.items() if e["case"]["cfg"].get("control_slack_mode")]
     for name in names:
@@ -163,7 +157,7 @@ def test_fov_slack_cases(mpclib, fov):
 
 def _conn_solve(torch, mpclib, cfg, ptr, states, desired, outputs=True):
     dev = torch.device("cuda", 0)
-    t = lambda v, dt=torch.float64: torch.tensor(np.ascontiguousarray(v), dtype=dt, device=dev)  # noqa: E731
+    t = lambda v, dt=torch.float64: to_device(v, dt)  # noqa: E731
     R, T = len(states), len(ptr) - 1
     u = torch.full((R + 1, 3), POISON, dtype=torch.float64, device=dev)
     status = torch.full((R + 1,), -77, dtype=torch.int32, device=dev)
@@ -193,7 +187,7 @@ def test_connectivity_cases(mpclib, oracle, slack):
     of about mu / 7.6e-4 ~ 1e-6, which moves u by that much; every other robot is within 1.5e-7;
     objective 4.5e-9; slack |obj - penalty(u)| 5.8e-9, penalty gap 5.8e-9, |u - oracle| 5.8e-7 (the
     same robot)."""
-    torch = _torch()
+    torch = require_gpu()
     cs = Cs.conn_cases(slack)
     cfg, ptr, states, desired = cs["cfg"], cs["team_ptr"], cs["states"], cs["desired"]
     got = _conn_solve(torch, mpclib, cfg, ptr, states, desired)

@@ -6,16 +6,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import require_gpu
 from mpccbf import swarm
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 def _expected_next(p, cfg, x_new, x_prev, t_prev, have, state):
@@ -35,7 +29,7 @@ def _expected_next(p, cfg, x_new, x_prev, t_prev, have, state):
 
 @pytest.mark.parametrize("fov", [False, True])
 def test_fallback_trajectory_bookkeeping(mpclib, fov):
-    torch = _torch()
+    torch = require_gpu()
     if fov:
         cfg = swarm.fov_config(20)
         states, targets = swarm.heading_swarm(96, seed=11)
@@ -81,7 +75,7 @@ def test_fallback_trajectory_bookkeeping(mpclib, fov):
 
 
 def test_run_steps_fallback_matches_step_by_step(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(256, seed=12)
     states[:, :2] *= 0.45
@@ -108,7 +102,7 @@ def test_run_steps_fallback_matches_step_by_step(mpclib):
 
 
 def test_state_noise_statistics_and_determinism(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(1024, seed=13)
     dev = torch.device("cuda", 0)
@@ -141,7 +135,7 @@ def test_launch_clock_per_wave(mpclib, n, variant):
     the launch durations (largest end - smallest start) are positive, below the HIP-event time of
     the same steps' kernels, and the clocked run gives the same closed loop as an unclocked one (the
     clock changes no result). A buffer with fewer pairs per step than the launch's waves is refused."""
-    torch = _torch()
+    torch = require_gpu()
     from mpccbf._lib import kernel_clock_us
     dev = torch.device("cuda", 0)
     cfg = swarm.config(15)

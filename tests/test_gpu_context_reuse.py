@@ -25,8 +25,9 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import _manual_loop, fresh_outputs, require_gpu, run_oracle, to_device, to_host
 from mpccbf import swarm
-from test_gpu_parity import _manual_loop, _torch, compare, run_oracle
+from parity_rule import check_parity, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -35,18 +36,11 @@ WIDE, SEP = "impc_wide_kernel<256>", "impc_sep_kernel<1,1,false,256>"
 OUT_KEYS = ("x", "status", "obj", "iters")
 
 
-def _fill_sentinel(torch, out):
-    """NaN / -7 in every output: what a launch leaves unwritten compares equal on both sides and
-    shows in the guarded tails."""
-    for v in out.values():
-        v.fill_(float("nan") if v.dtype == torch.float64 else -7)
-
-
 def _csr_device(torch, dev, rp, col, first=0, count=None):
     """Device CSR lists of agents [first, first + count) (row_ptr[0] may be nonzero)."""
     count = len(rp) - 1 - first if count is None else count
-    return dict(nb_row_ptr=torch.tensor(np.ascontiguousarray(rp[first:first + count + 1]), device=dev),
-                nb_col=torch.tensor(col if len(col) else np.zeros(1, np.int32), device=dev))
+    return dict(nb_row_ptr=to_device(rp[first:first + count + 1]),
+                nb_col=to_device(col))
 
 
 # ---- (a) continuation after a foreign write ----------------------------------------------------
@@ -110,7 +104,7 @@ def test_continuation_after_foreign_write_rebuilds(mpclib, first, count, interlu
     neighbour table changed no result and that refill passed on the library without the fix (0 of
     256 final rows differed). With the 0.45 refill 165 / 156 of 256 final rows differed there, and
     17 of 256 in each of the other two cases."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(256, seed=6)
     states[:, :2] *= 0.6
@@ -129,10 +123,10 @@ def test_continuation_after_foreign_write_rebuilds(mpclib, first, count, interlu
     assert not np.any(ref_log == -7)
     if interlude == "zero_step":  # the last call starts from the refilled table: 4 steps one by one
         loop, loop_status = _manual_loop(mpclib.Context(cfg), refill, tg, 4, first, count, torch)
-        np.testing.assert_array_equal(ref, loop)
-        np.testing.assert_array_equal(ref_log[-1], loop_status)
-    np.testing.assert_array_equal(got, ref)
-    np.testing.assert_array_equal(got_log, ref_log)
+        same_bits(ref, loop)
+        same_bits(ref_log[-1], loop_status)
+    same_bits(got, ref)
+    same_bits(got_log, ref_log)
 
 
 # ---- (b) FoV continuation ----------------------------------------------------------------------
@@ -143,7 +137,7 @@ def test_fov_run_steps_continuation_matches_one_call(mpclib, slack):
     (impc_fov_kernel<false|true>, which bench.py runs through a continuation): 3 + 4 + 5 steps in
     three calls, continuing, and with a grid-mode impc_solve between the second and third call
     (which then rebuilds), == 12 steps in one call: bit-identical states and statuses."""
-    torch = _torch()
+    torch = require_gpu()
     over = dict(slack_mode=1, slack_cost=1000.0, slack_decay_rate=0.5) if slack else {}
     cfg = swarm.fov_config(20, **over)
     n = 256
@@ -177,8 +171,8 @@ def test_fov_run_steps_continuation_matches_one_call(mpclib, slack):
                 a, b = b, a
             s += k
         torch.cuda.synchronize()
-        np.testing.assert_array_equal(a.cpu().numpy(), ref, err_msg=mode)
-        np.testing.assert_array_equal(log2.cpu().numpy(), ref_log, err_msg=mode)
+        same_bits(a.cpu().numpy(), ref, what=mode)
+        same_bits(log2.cpu().numpy(), ref_log, what=mode)
 
 
 # ---- (c) call sequences on one context ---------------------------------------------------------
@@ -251,8 +245,7 @@ def _run_op(ctx, cfg, op, inputs, torch):
         kw.update(knn_k=K, knn_radius=cfg["fov_Rs"] if cfg["cbf_mode"] == 1 else RADIUS)
     else:
         kw.update(_csr_device(torch, dev, lists[0], lists[1], first, count))
-    out = {k: v for k, v in ctx.alloc_outputs(count).items() if k in OUT_KEYS}
-    _fill_sentinel(torch, out)
+    out = {k: v for k, v in fresh_outputs(ctx, count).items() if k in OUT_KEYS}
     torch.cuda.synchronize()
     stream = torch.cuda.Stream(device=dev) if op["stream"] else None
     if op["kind"] == "run3":
@@ -264,7 +257,7 @@ def _run_op(ctx, cfg, op, inputs, torch):
         nxt = torch.full((count, 6), float("nan"), dtype=torch.float64, device=dev)
         ctx.impc_solve(st, next_states=nxt, stream=stream, **kw, **out)
         torch.cuda.synchronize()
-    res = {k: v.cpu().numpy() for k, v in out.items()}
+    res = to_host(out)
     res["next"] = nxt.cpu().numpy()
     return res
 
@@ -288,8 +281,7 @@ def _run_sequence(mpclib, torch, cfg, ops):
         assert fresh.kernel_name == names[-1], (i, fresh.kernel_name, names[-1])
         fresh.close()
         assert not np.any(ref["status"] == -7), (i, op)
-        for k in OUT_KEYS + ("next",):
-            np.testing.assert_array_equal(got[k], ref[k], err_msg=f"operation {i} {op}: {k}")
+        same_bits(got, ref, keys=OUT_KEYS + ("next",), what=f"operation {i} {op}")
         results.append(got)
     return names, results
 
@@ -302,7 +294,7 @@ def test_collision_call_sequence_matches_fresh_contexts(mpclib):
     each give x, status, obj, iters and the next states of the same operation alone on a fresh
     Context, bit for bit: nothing the context carries (grown grid scratch, deferral queues and their
     parity, continuation record, variant and last launch size) leaks into a result."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     assert len(COLLISION_OPS) >= 12 and sum(op["stream"] for op in COLLISION_OPS) >= 2
     names, results = _run_sequence(mpclib, torch, cfg, COLLISION_OPS)
@@ -320,7 +312,7 @@ def test_collision_call_sequence_matches_fresh_contexts(mpclib):
 def test_fov_call_sequence_matches_fresh_contexts(mpclib, slack):
     """The same for a FoV Context (impc_fov_kernel<false|true>): grid and CSR calls, single solves
     and 3-step runs, tables of 64, 300, 17 and 1 agents, mixed on one context."""
-    torch = _torch()
+    torch = require_gpu()
     over = dict(slack_mode=1, slack_cost=1000.0, slack_decay_rate=0.5) if slack else {}
     cfg = swarm.fov_config(20, **over)
     names, results = _run_sequence(mpclib, torch, cfg, FOV_OPS)
@@ -351,7 +343,7 @@ def _small_case(n, scale):
 def small_sweep(mpclib):
     """Every (variant, mode, scale, n) of the sweep solved once, one Context per variant, every
     output and the next-state table allocated for n + 7 agents and filled with a sentinel."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     cfg = swarm.config(15)
     res = {}
@@ -363,12 +355,11 @@ def small_sweep(mpclib):
                 states, targets, rp, col, _ = _small_case(n, scale)
                 st, tg = torch.tensor(states, device=dev), torch.tensor(targets, device=dev)
                 for mode in ("csr", "grid"):
-                    out = ctx.alloc_outputs(n + GUARD)
-                    _fill_sentinel(torch, out)
+                    out = fresh_outputs(ctx, n + GUARD)
                     nb = _csr_device(torch, dev, rp, col) if mode == "csr" else dict(knn_k=K, knn_radius=RADIUS)
                     ctx.impc_solve(st, targets=tg, num_agents=n, **nb, **out)
                     torch.cuda.synchronize()
-                    res[variant, mode, scale, n] = ({k: v.cpu().numpy() for k, v in out.items()}, ctx.kernel_name)
+                    res[variant, mode, scale, n] = (to_host(out), ctx.kernel_name)
     return res
 
 
@@ -388,7 +379,7 @@ def test_small_agent_counts_match_oracle_with_guarded_tails(small_sweep, variant
             g, name = small_sweep[variant, mode, scale, n]
             assert name == (SEP if variant == 4 else WIDE), (variant, n, name)
             ref = _small_case(n, scale)[4]
-            compare(cfg, {k: v[:n] for k, v in g.items()}, ref, list(range(n)))
+            check_parity({k: v[:n] for k, v in g.items()}, ref, list(range(n)))
             for k, v in g.items():
                 tail = v[n:]
                 assert tail.shape[0] == GUARD
@@ -422,7 +413,7 @@ def test_small_agent_counts_cover_hard_qps(small_sweep):
 def test_prepared_run_timings_survive_the_next_call(mpclib):
     """PreparedRun.__call__ hands out step_ms and solve_ms as copies: the library overwrites its
     host buffers at the next call, which must not change (or alias) an earlier result."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(64, seed=6)
     states[:, :2] *= 0.6
@@ -466,7 +457,7 @@ def test_solve_stride_times_every_other_solve_and_changes_no_result(mpclib):
     step (the margin of test_run_steps_matches_step_by_step); solve_stride = 1 times all 5. Which
     events a call records changes nothing it computes: the final table, the status log and x of
     both timed runs equal those of an untimed run, bit for bit."""
-    torch = _torch()
+    torch = require_gpu()
     _, plain = _timed_run(mpclib, torch, timing=False)
     assert not np.any(plain[1] == -7)
     every, got1 = _timed_run(mpclib, torch, timing=True, solve_stride=1)
@@ -481,4 +472,4 @@ def test_solve_stride_times_every_other_solve_and_changes_no_result(mpclib):
     assert np.all(other["solve_ms"] <= other["step_ms"][[0, 2, 4]] + 1e-3)
     for got in (got1, got2):
         for g, p, name in zip(got, plain, ("final table", "status log", "x")):
-            np.testing.assert_array_equal(g, p, err_msg=name)
+            same_bits(g, p, what=name)

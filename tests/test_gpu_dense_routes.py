@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import dense_route_cases as C
+from parity_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -33,13 +34,12 @@ def _compare(mpclib, got, k, q, ref=None, where=""):
     assert np.max(np.abs(xs[k] - r["x"])) <= 1e-5, (where, k, np.max(np.abs(xs[k] - r["x"])))
 
 
-def _same_bits(a, b):
+def _same_bits(a, b, what=""):
     """Two results of one QP (status, x or None, objective): bit-identical (NaN by bit pattern)."""
-    if a[0] != b[0] or (a[1] is None) != (b[1] is None):
-        return False
-    if a[1] is not None and not np.array_equal(a[1].view(np.uint64), b[1].view(np.uint64)):
-        return False
-    return np.float64(a[2]).view(np.uint64) == np.float64(b[2]).view(np.uint64)
+    assert a[0] == b[0] and (a[1] is None) == (b[1] is None), (what, a[0], b[0])
+    same_bits(np.float64(a[2]), np.float64(b[2]), what=what)
+    if a[1] is not None:
+        same_bits(a[1], b[1], what=what)
 
 
 def _qp(got, k):
@@ -47,7 +47,9 @@ def _qp(got, k):
 
 
 def _identical_calls(a, b):
-    return len(a[0]) == len(b[0]) and all(_same_bits(_qp(a, k), _qp(b, k)) for k in range(len(a[0])))
+    assert len(a[0]) == len(b[0])
+    for k in range(len(a[0])):
+        _same_bits(_qp(a, k), _qp(b, k), what=k)
 
 
 def test_reduced_dimension_1_to_8(mpclib, oracle):
@@ -123,7 +125,7 @@ def test_base_set_on_every_route(mpclib, oracle, route_results, name):
     for k, (q, tag) in enumerate(zip(qps, tags)):
         _compare(mpclib, got, k, q, where=f"call {name}, base {tag}")
         if tag in first:
-            assert _same_bits(_qp(got, first[tag]), _qp(got, k)), (name, tag, first[tag], k)
+            _same_bits(_qp(got, first[tag]), _qp(got, k), what=(name, tag, first[tag], k))
         else:
             first[tag] = k
     assert got[0][tags.index(C.BASE_INFEASIBLE)] == mpclib.INFEASIBLE
@@ -174,12 +176,11 @@ def test_call_sequence_on_one_thread(mpclib, oracle):
     in mid-pipeline: a large call, a single QP, a small call, a call that fails in its second slice
     (invalid QPs 300 and 900 of 1027: the error names the first), a capacity error, then the small
     and the large call again, each bit for bit what it returned the first time."""
-    from test_dense_qp import toy
     calls = C.route_calls()
     big, small = calls["e"][0], calls["a"][0]
     fail = C.failing_calls()
     big1 = mpclib.dense_qp_solve_batch(big)
-    st, x, obj = mpclib.dense_qp_solve(**toy())
+    st, x, obj = mpclib.dense_qp_solve(**C.toy())
     assert st == mpclib.OPTIMAL and abs(obj - 0.5) < 1e-8
     np.testing.assert_allclose(x, [0.5, 0.5], atol=1e-6)
     small1 = mpclib.dense_qp_solve_batch(small)
@@ -193,8 +194,8 @@ def test_call_sequence_on_one_thread(mpclib, oracle):
         _compare(mpclib, small1, k, q, where="small, first")
     for k, q in enumerate(big):
         _compare(mpclib, big1, k, q, where="large, first")
-    assert _identical_calls(small1, small2)
-    assert _identical_calls(big1, big2)
+    _identical_calls(small1, small2)
+    _identical_calls(big1, big2)
 
 
 def test_fresh_thread_grows_every_buffer_from_nothing(mpclib, route_results):
@@ -227,6 +228,7 @@ def test_fresh_thread_grows_every_buffer_from_nothing(mpclib, route_results):
     for r in (main_one, got[0], got[3]):
         assert r[0][0] == mpclib.OPTIMAL
         assert abs(r[1][0][0] + c / (2.0 * h)) <= 1e-5 and abs(r[2][0] + c * c / (4.0 * h)) <= 1e-6
-    assert _identical_calls(got[0], main_one) and _identical_calls(got[3], main_one)
-    assert _identical_calls(got[1], route_results["d"])
-    assert _identical_calls(got[2], route_results["e"])
+    _identical_calls(got[0], main_one)
+    _identical_calls(got[3], main_one)
+    _identical_calls(got[1], route_results["d"])
+    _identical_calls(got[2], route_results["e"])

@@ -25,7 +25,8 @@ import pytest
 import exact_geometry_cases as X
 import oracle_lib as O
 from mpccbf import swarm
-from test_gpu_parity import _torch, compare, run_gpu, run_oracle
+from gpu_harness import require_gpu, run_gpu, run_oracle, to_host
+from parity_rule import ROUTE_REL, check_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -54,13 +55,13 @@ def _ctx(mpclib, variant, fov=False, slack=0):
 
 
 def _host(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return to_host(out)
 
 
 def _solve(ctx, states, targets, k=0, radius=0.0, rp=None, col=None, first=0, count=None):
     """One impc_solve of agents [first, first + count): grid mode (k, radius) or CSR lists (the
     agents' own rows). Returns host outputs with nb_out (initialised to SENTINEL) and the kernel."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     count = len(states) - first if count is None else count
     st = torch.tensor(states, dtype=torch.float64, device=dev)
@@ -161,7 +162,7 @@ def test_fov_nb_out_equals_cpu_lists(mpclib, k, radius, slack):
 
 
 def _build(ctx, states, first, count, k, radius):
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     n = len(states)
     st = torch.tensor(states, dtype=torch.float64, device=dev)
@@ -228,7 +229,7 @@ def test_tie_control_matches_oracle(mpclib):
     ref = run_oracle(cfg, st, tg, rp, col, agents)
     assert not any(r["status"][it] == O.UNKNOWN for r in ref for it in range(r["attempted"]))
     for variant in KERNELS:
-        compare(cfg, _grid(mpclib, case, variant), ref, agents)
+        check_parity(_grid(mpclib, case, variant), ref, agents)
 
 
 @pytest.mark.parametrize("variant", [0, 3, 4])
@@ -236,7 +237,7 @@ def test_run_steps_nb_out_equals_lists_of_the_table_read(mpclib, variant):
     """Two closed-loop steps: the second reads the neighbour table the first step's kernel filled
     itself (grid_insert); its nb_out == knn_csr of the state table it read. Jittered on purpose:
     after one step the coordinates are no longer exact."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     states, targets = swarm.lattice_swarm(144)
     states[:, :2] *= 0.55
@@ -300,10 +301,10 @@ def test_duplicate_and_coincident_neighbours(mpclib, variant):
             err = np.abs(g["obj"][ok] - u["obj"][ok]) / np.maximum(1.0, np.abs(u["obj"][ok]))
             dx = np.max(np.abs(g["x"] - u["x"]))
             print(f"{name} variant {variant} vs {other}: obj rel {err.max():.3e}, x {dx:.3e}")
-            assert err.max() <= 1e-7, (what, err.max())
+            assert err.max() <= ROUTE_REL, (what, err.max())
             assert dx <= 1e-6, (what, dx)
-            compare(cfg, u, ref, [0])
-        compare(cfg, g, ref, [0])
+            check_parity(u, ref, [0])
+        check_parity(g, ref, [0])
 
 
 @pytest.mark.parametrize("kind", ["shear", "centre"])
@@ -314,9 +315,9 @@ def test_symmetric_lattice_matches_oracle(mpclib, variant, kind):
     cfg = swarm.config(15)
     st, tg, rp, col = X.dependent_lattice(kind)
     ref = X.oracle_agents(cfg, st, tg, rp, col, range(64), key=("lattice", kind))
-    g = run_gpu(_ctx(mpclib, variant), st, tg, rp, col, _torch())
+    g = run_gpu(_ctx(mpclib, variant), st, tg, rp, col, require_gpu())
     _sure(g)
-    compare(cfg, g, ref, list(range(64)))
+    check_parity(g, ref, list(range(64)))
 
 
 @pytest.mark.parametrize("variant,kernel", [(4, "impc_sep_store_kernel<1,256,false>"),
@@ -324,7 +325,7 @@ def test_symmetric_lattice_matches_oracle(mpclib, variant, kind):
 def test_active_store_record_has_no_repeated_side(mpclib, variant, kernel):
     """With an active-set store attached, the exported record of a solve on [1, 1, 1, 1] and on
     the twins [1, 2] holds at most 5 sides and no key twice, and the solve is the oracle's."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     ctx = mpclib.Context(cfg)
     ctx.set_variant(variant)
@@ -338,7 +339,7 @@ def test_active_store_record_has_no_repeated_side(mpclib, variant, kernel):
         g = _point(ctx, target, lst)
         assert g["kernel"] == kernel
         _sure(g)
-        compare(cfg, g, [X.oracle_point(cfg, target, X.unique_sorted(lst))], [0])
+        check_parity(g, [X.oracle_point(cfg, target, X.unique_sorted(lst))], [0])
         rec = store.cpu().numpy()[0]
         k = int(rec[0])
         keys = [int(v) for v in rec[1:1 + max(k, 0)]]

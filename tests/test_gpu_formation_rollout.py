@@ -10,7 +10,9 @@ import pytest
 
 import formation_rollout_cases as F
 import oracle_lib as O
+from gpu_harness import to_device, to_host
 from mpccbf import metrics
+from parity_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +33,7 @@ def run_raw(mpclib, cfg, team_ptr, states, targets, seeds, steps, step_first=0, 
     dev = torch.device("cuda", 0)
     team_ptr = np.ascontiguousarray(team_ptr, dtype=np.int32)
     n, teams = int(team_ptr[-1]), len(team_ptr) - 1
-    t = lambda a, dt=None: torch.tensor(np.ascontiguousarray(a, dtype=dt), device=dev)  # noqa: E731
+    t = lambda a, dt=None: to_device(np.asarray(a, dtype=dt))  # noqa: E731
     d_states = t(states, np.float64)
     rec = {k: torch.full((steps, n) + WIDTH[k], FILL, dtype=torch.int32 if k in ("status", "iters") else torch.float64,
                          device=dev) for k in records}
@@ -44,18 +46,14 @@ def run_raw(mpclib, cfg, team_ptr, states, targets, seeds, steps, step_first=0, 
                              Ts=cfg["Ts"], pos_std=pos_std, vel_std=vel_std, shape_half=shape_half,
                              goal_radius=goal_radius, steps_per_launch=steps_per_launch, **rec, **summ)
     torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in rec.items()}
-    out.update({k: v.cpu().numpy() for k, v in summ.items()})
+    out = to_host(rec)
+    out.update(to_host(summ))
     out["states"] = d_states.cpu().numpy()
     return out
 
 
 def team_rec(rec, r0, r1):
     return {k: rec[k][:, r0:r1] for k in RECORDS if k in rec}
-
-
-def same_bits(a, b, keys):
-    return [k for k in keys if a[k].tobytes() != b[k].tobytes()]
 
 
 def check_batch(cfg, states, targets, team_ptr, seeds, rec, step_first=0, skip=(), **noise):
@@ -168,7 +166,7 @@ def test_from_instances_on_the_base_config(mpclib):
         r0, r1 = int(obj.team_ptr_host[t]), int(obj.team_ptr_host[t + 1])
         alone = run_raw(mpclib, obj.cfg, [0, r1 - r0], states, targets, [seeds[t % 3]], 3, shape_half=shape[:2], **noise)
         for k in RECORDS:
-            assert alone[k].tobytes() == np.ascontiguousarray(rec[k][:, r0:r1]).tobytes(), (t, k)
+            same_bits(alone[k], rec[k][:, r0:r1], what=(t, k))
     assert rec["trace"][:, 0:2].tobytes() != rec["trace"][:, 2:4].tobytes()
     assert len(obj.results()) == 6
     # that first decision of 5r/circle is the batched controller's own answer on the same table
@@ -222,9 +220,9 @@ def test_oversize_and_empty_teams(mpclib):
     r0, r1 = int(team_ptr[1]), int(team_ptr[2])
     assert np.all(rec["status"][:, r0:r1] == O.ERROR) and np.all(rec["iters"][:, r0:r1] == 0)
     assert np.all(np.isnan(rec["cbf_u"][:, r0:r1])) and np.all(np.isnan(rec["lambda2"][:, r0:r1]))
-    assert rec["states"][r0:r1].tobytes() == states[r0:r1].tobytes()
+    same_bits(rec["states"][r0:r1], states[r0:r1])
     for s in range(steps):
-        assert rec["trace"][s, r0:r1].tobytes() == states[r0:r1].tobytes()
+        same_bits(rec["trace"][s, r0:r1], states[r0:r1])
         want = np.array([F.desired_control(states[i], targets[i]) for i in range(r0, r1)])
         assert np.allclose(rec["desired_u"][s, r0:r1], want, rtol=1e-12, atol=1e-12)
     others = np.ones(team_ptr[-1], dtype=bool)
@@ -252,14 +250,14 @@ def test_zero_steps_and_one_step(mpclib):
     cfg = F.edge_cfg()
     states, targets, team_ptr, seeds = F.edge_batch([3, 5])
     rec = run_raw(mpclib, cfg, team_ptr, states, targets, seeds, 0)
-    assert rec["states"].tobytes() == states.tobytes()
+    same_bits(rec["states"], states)
     assert np.all(rec["arrival_sample"] == -1) and np.all(rec["first_collision"] == -1)
     assert np.all(rec["min_d2"] == np.inf) and np.all(rec["fail_count"] == 0)
     assert all(rec[k].shape[0] == 0 for k in RECORDS)
     rec = run_raw(mpclib, cfg, team_ptr, states, targets, seeds, 1)
     bad, seen = check_batch(cfg, states, targets, team_ptr, seeds, rec)
     assert seen == 8 and not bad, bad[:5]
-    assert rec["states"].tobytes() == rec["trace"][0].tobytes()
+    same_bits(rec["states"], rec["trace"][0])
     assert np.all(np.isfinite(rec["min_d2"]))
 
 
@@ -281,16 +279,16 @@ def test_split_and_chained_calls_change_nothing(mpclib, indep):
     cfg, states, targets, team_ptr, seeds, base = indep
     assert not np.any(base["trace"] == FILL)
     again = run_raw(mpclib, cfg, team_ptr, states, targets, seeds, INDEP_STEPS)
-    assert same_bits(base, again, ALL) == []
+    same_bits(base, again, ALL)
     for per in (1, 7, 32):  # (32: one launch)
         got = run_raw(mpclib, cfg, team_ptr, states, targets, seeds, INDEP_STEPS, steps_per_launch=per)
-        assert same_bits(base, got, ALL) == [], per
+        same_bits(base, got, ALL, what=per)
     a = run_raw(mpclib, cfg, team_ptr, states, targets, seeds, 12)
     b = run_raw(mpclib, cfg, team_ptr, a["states"], targets, seeds, 8, step_first=12,
                 summary={k: a[k] for k in SUMMARY})
     chained = {k: np.concatenate([a[k], b[k]]) for k in RECORDS}
     chained.update({k: b[k] for k in SUMMARY + ("states",)})
-    assert same_bits(base, chained, ALL) == []
+    same_bits(base, chained, ALL)
 
 
 def test_a_team_alone_equals_the_team_in_a_batch(mpclib, indep):
@@ -300,11 +298,11 @@ def test_a_team_alone_equals_the_team_in_a_batch(mpclib, indep):
     assert r1 - r0 == INDEP_SIZES[17] >= 2
     alone = run_raw(mpclib, cfg, [0, r1 - r0], states[r0:r1], targets[r0:r1], [seeds[t]], INDEP_STEPS)
     for k in RECORDS:
-        assert alone[k].tobytes() == np.ascontiguousarray(base[k][:, r0:r1]).tobytes(), k
-    assert alone["states"].tobytes() == base["states"][r0:r1].tobytes()
+        same_bits(alone[k], base[k][:, r0:r1], what=k)
+    same_bits(alone["states"], base["states"][r0:r1])
     assert alone["arrival_sample"].tolist() == base["arrival_sample"][r0:r1].tolist()
     for k in ("first_collision", "min_d2", "fail_count"):
-        assert alone[k][0].tobytes() == base[k][t].tobytes(), k
+        same_bits(alone[k][0], base[k][t], what=k)
     # another seed is another run
     other = run_raw(mpclib, cfg, [0, r1 - r0], states[r0:r1], targets[r0:r1], [seeds[t] + 1], INDEP_STEPS)
     assert other["trace"].tobytes() != alone["trace"].tobytes()
@@ -328,7 +326,7 @@ def test_optional_outputs_change_nothing(mpclib, slack):
     for rec, summ in cases:
         got = run(rec, summ)
         assert set(got) == set(rec) | set(summ) | {"states"}
-        assert same_bits(base, got, tuple(rec) + tuple(summ) + ("states",)) == [], (rec, summ)
+        same_bits(base, got, tuple(rec) + tuple(summ) + ("states",), what=(rec, summ))
 
 
 # ---- 5. summary --------------------------------------------------------------------------------
@@ -390,4 +388,4 @@ def test_to_json_is_the_examples_record(parity_runs):
         assert len(js["robots"][str(i)]["states"][0]) == 6 and len(js["robots"][str(i)]["cbf_u"][0]) == 3
     r0 = int(obj.team_ptr_host[t])
     back = metrics.trajectories_from_states_json(js)
-    assert back.tobytes() == np.ascontiguousarray(rec["trace"][:, r0:r0 + n].transpose(1, 0, 2)).tobytes()
+    same_bits(back, rec["trace"][:, r0:r0 + n].transpose(1, 0, 2))

@@ -2,8 +2,8 @@
 set_fov_estimator; impc_fov_kernel<SLACK, true>) on the inputs of tests/fov_estimate_cases.py.
 
 The reference is the unchanged oracle on a per-observer copy of the state table (oracle_reference
-there): statuses equal, objectives within OBJ_TOL relative. "Bit-identical" is torch.equal with NaN
-matching NaN. Every case stays at the base FoV configuration and at most 33 agents."""
+there): statuses equal, objectives within OBJ_TOL relative. "Bit for bit" is parity_rule.same_bits.
+Every case stays at the base FoV configuration and at most 33 agents."""
 import functools
 
 import numpy as np
@@ -12,7 +12,8 @@ import pytest
 import fov_estimate_cases as F
 import oracle_lib as O
 from mpccbf import swarm
-from test_gpu_parity import OBJ_TOL, _torch
+from gpu_harness import Solver, require_gpu, same_bits, same_values, to_device, to_host
+from parity_rule import check_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -33,83 +34,33 @@ def _oracle(kind, key, setting):
     return F.oracle_batch(F.config(setting), case)
 
 
-def _dev(torch, a, dtype=None):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=torch.device("cuda", 0))
-
-
-def _same(torch, a, b):
-    if a.is_floating_point():
-        return bool(torch.all((a == b) | (torch.isnan(a) & torch.isnan(b))))
-    return torch.equal(a, b)
-
-
-def _assert_same(torch, got, want, what, rows=None):
-    for k in OUTS:
-        a, b = (got[k], want[k]) if rows is None else (got[k][rows], want[k][rows])
-        assert _same(torch, a, b), (what, k)
-
-
-class Solver:
-    """One case on one context: the device copies of its tables and a solve that returns fresh,
-    pre-filled outputs."""
-
-    def __init__(self, mpclib, cfg, case):
-        self.torch = torch = _torch()
-        self.ctx = mpclib.Context(cfg)
-        self.case = c = case
-        self.states = _dev(torch, c["states"])
-        self.targets = _dev(torch, c["targets"])
-        self.rp = _dev(torch, c["rp"], torch.int32)
-        self.col = _dev(torch, c["col"] if len(c["col"]) else np.zeros(1, np.int32), torch.int32)
-        self.nb_xy = _dev(torch, c["nb_xy"])
-        self.nb_cov = _dev(torch, c["nb_cov"])
-
-    def solve(self, cov=None, grid=False):
-        torch, c, n = self.torch, self.case, self.case["num_agents"]
-        out = self.ctx.alloc_outputs(n)
-        for v in out.values():
-            v.fill_(float("nan") if v.is_floating_point() else -7)
-        out["nb_out"] = torch.full((n, 16), -7, dtype=torch.int32, device=self.states.device)
-        lists = dict(knn_k=8, knn_radius=6.0) if grid else dict(nb_row_ptr=self.rp, nb_col=self.col)
-        self.ctx.impc_solve(self.states, targets=self.targets, agent_first=c["agent_first"], num_agents=n,
-                            cov=cov, **lists, **out)
-        torch.cuda.synchronize()
-        return out
-
-
 def _assert_matches_oracle(out, ref, what):
-    st, ob = out["status"].cpu().numpy(), out["obj"].cpu().numpy()
-    rst, rob = ref
-    for a in range(len(rst)):
-        print(what, a, st[a], rst[a], ob[a], rob[a])
-        assert list(st[a]) == list(rst[a]), (what, a, st[a], rst[a])
-        for k in range(rst.shape[1]):
-            if rst[a, k] == O.OPTIMAL:
-                assert abs(ob[a, k] - rob[a, k]) <= OBJ_TOL * max(1.0, abs(rob[a, k])), (what, a, k, ob[a, k], rob[a, k])
+    """Statuses and objectives (the oracle batches here carry no curves)."""
+    check_parity(to_host(out), ref, label=what, x=False)
 
 
 @pytest.mark.parametrize("setting", ["plain", "slack"])
 def test_true_positions_attached_are_the_unattached_solve(mpclib, setting):
     """Identity: estimates equal to the table's positions and covariances give the unattached solve
     bit for bit, through the estimate form; after a detach the old kernel runs again."""
-    torch = _torch()
+    torch = require_gpu()
     c = dict(F.swarm_case(33))
     cov_table = F.random_spd(np.random.default_rng(3), 33)
     c["nb_xy"], c["nb_cov"] = c["states"][c["col"], :2], cov_table[c["col"]]
     s = Solver(mpclib, F.config(setting), c)
-    cov = _dev(torch, cov_table)
+    cov = to_device(cov_table)
     plain = s.solve(cov=cov)
     assert s.ctx.kernel_name == OLD_NAME[setting]
     s.ctx.set_fov_estimates(s.nb_xy, s.nb_cov)
     junk = torch.full_like(cov, 7.5)  # (batch.cov is ignored while attached)
     est = s.solve(cov=junk)
     assert s.ctx.kernel_name == EST_NAME[setting]
-    _assert_same(torch, est, plain, "attached")
+    same_bits(est, plain, keys=OUTS, what="attached")
     assert int((plain["status"] == O.OPTIMAL).sum()) > 33  # (the comparison is of solved QPs)
     s.ctx.set_fov_estimates(None)
     again = s.solve(cov=cov)
     assert s.ctx.kernel_name == OLD_NAME[setting]
-    _assert_same(torch, again, plain, "detached")
+    same_bits(again, plain, keys=OUTS, what="detached")
 
 
 @pytest.mark.parametrize("setting", ["plain", "slack"])
@@ -142,7 +93,7 @@ def test_pair_offsets_and_caps(mpclib, oracle, setting):
         _assert_matches_oracle(s.solve(), _oracle("fans", ks, setting), f"fans{ks}/{setting}")
     over = F.FAN_OVER_CAP[setting]
     s = Solver(mpclib, cfg, _fans((2, over)))
-    today = s.solve(cov=_dev(s.torch, s.case["cov_table"]))
+    today = s.solve(cov=to_device(s.case["cov_table"]))
     s.ctx.set_fov_estimates(s.nb_xy, s.nb_cov)
     est = s.solve()
     print("over the cap:", est["status"][1].tolist(), today["status"][1].tolist())
@@ -170,7 +121,7 @@ def test_slack_order_is_per_pair(mpclib, oracle):
 
 @pytest.mark.parametrize("setting", ["plain", "slack"])
 def test_guards(mpclib, setting):
-    torch = _torch()
+    torch = require_gpu()
     c = F.swarm_case(33)
     s = Solver(mpclib, F.config(setting), c)
     # the collision controller has no estimates
@@ -191,7 +142,7 @@ def test_guards(mpclib, setting):
     others = torch.tensor([a for a in range(33) if a != last], device=s.states.device)
     assert int(short["status"][last, 0]) == O.ERROR
     assert not bool((short["status"][others] == O.ERROR).any())
-    _assert_same(torch, short, full, "one pair short", rows=others)
+    same_values(short, full, keys=OUTS, what="one pair short", rows=others)
     # one non-finite estimate: its observer alone reports ERROR
     a = int(np.argmax(np.diff(rp)))
     bad_xy = s.nb_xy.clone()
@@ -200,22 +151,22 @@ def test_guards(mpclib, setting):
     nan = s.solve()
     others = torch.tensor([b for b in range(33) if b != a], device=s.states.device)
     assert int(nan["status"][a, 0]) == O.ERROR
-    _assert_same(torch, nan, full, "one NaN estimate", rows=others)
+    same_values(nan, full, keys=OUTS, what="one NaN estimate", rows=others)
     s.ctx.set_fov_estimates(None)
     s.solve(grid=True)  # (detached: grid mode again)
 
 
 def _loop_state(mpclib, cfg, c, seed):
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     n = c["num_agents"]
     ctx = mpclib.Context(cfg)
     est = mpclib.FovEstimator(dict(cfg, pf_num_particles=100), c["rp"], c["col"], n, seed=seed)
-    a = _dev(torch, c["states"])
+    a = to_device(c["states"])
     est.init(a)
     out = ctx.alloc_outputs(n)
     out["x"].fill_(float("nan"))
-    return dict(ctx=ctx, est=est, a=a, b=torch.empty_like(a), tg=_dev(torch, c["targets"]),
+    return dict(ctx=ctx, est=est, a=a, b=torch.empty_like(a), tg=to_device(c["targets"]),
                 traj_t=torch.full((n,), -1.0, dtype=torch.float64, device=dev), out=out,
                 slog=torch.full((5, n, 2), -7, dtype=torch.int32, device=dev),
                 ilog=torch.full((5, n, 2), -7, dtype=torch.int32, device=dev))
@@ -225,7 +176,7 @@ NOISE = dict(pos_std=0.001, vel_std=0.01, noise_seed=20251015)
 
 
 def _run_attached(mpclib, cfg, c, seed):
-    torch = _torch()
+    torch = require_gpu()
     L = _loop_state(mpclib, cfg, c, seed)
     L["ctx"].set_fov_estimator(L["est"])
     o = L["out"]
@@ -239,7 +190,7 @@ def _run_attached(mpclib, cfg, c, seed):
 
 
 def _run_python_loop(mpclib, cfg, c, seed):
-    torch = _torch()
+    torch = require_gpu()
     L = _loop_state(mpclib, cfg, c, seed)
     est, o = L["est"], L["out"]
     L["ctx"].set_fov_estimates(est.est_xy, est.est_cov)
@@ -259,7 +210,7 @@ def _run_python_loop(mpclib, cfg, c, seed):
 def test_filter_in_the_loop_is_the_python_loop(mpclib, setting):
     """run_steps with the estimator attached is est.step(states); impc_solve(...) step by step, bit
     for bit, and repeats bit for bit from the same seed."""
-    torch = _torch()
+    torch = require_gpu()
     cfg, c = F.config(setting), F.swarm_case(33)
     runs = [_run_attached(mpclib, cfg, c, 11), _run_python_loop(mpclib, cfg, c, 11), _run_attached(mpclib, cfg, c, 11)]
     assert runs[0]["ctx"].kernel_name == EST_NAME[setting]
@@ -269,10 +220,10 @@ def test_filter_in_the_loop_is_the_python_loop(mpclib, setting):
     assert not torch.equal(ref["final"], ref["a"])
     for name, other in (("python loop", runs[1]), ("second run", runs[2])):
         for k in ("final", "slog", "ilog", "traj_t"):
-            assert _same(torch, other[k], ref[k]), (name, k)
-        assert _same(torch, other["out"]["x"], ref["out"]["x"]), (name, "x")
+            same_bits(other[k], ref[k], what=(name, k))
+        same_bits(other["out"]["x"], ref["out"]["x"], what=(name, "x"))
         for k in ("est_xy", "est_cov", "particles", "weights", "flags"):
-            assert _same(torch, getattr(other["est"], k), getattr(ref["est"], k)), (name, k)
+            same_bits(getattr(other["est"], k), getattr(ref["est"], k), what=(name, k))
     # the estimates are not the true positions: the filter, not the table, fed the planner
     true = ref["final"][torch.as_tensor(c["col"], device=ref["final"].device).long(), :2]
     assert float((ref["est"].est_xy[:len(c["col"])] - true).abs().max()) > 1e-3

@@ -7,8 +7,8 @@ control points within X_TOL: the suite's rule). Where slacks are in use at objec
 more the objective is judged by the penalty objective (fov_param_cases.penalty_objective): the
 device's curve must keep the hard rows to 1e-6, cost no more than OBJ_TOL relative above the
 oracle's curve evaluated the same way, and its reported objective must be its own penalty objective
-to 1e-6 relative. "Bit-identical" is torch.equal with NaN matching NaN. One launch per swarm or fan
-batch, every agent compared."""
+to 1e-6 relative. "Bit for bit" is parity_rule.same_bits. One launch per swarm or fan batch, every
+agent compared."""
 import functools
 import math
 
@@ -17,7 +17,8 @@ import pytest
 
 import fov_param_cases as P
 import oracle_lib as O
-from test_gpu_parity import OBJ_TOL, X_TOL, _torch
+from gpu_harness import Solver as _Solver, same_bits, same_values, to_device, to_host
+from parity_rule import OBJ_TOL, ROUTE_REL, X_TOL, check_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -25,57 +26,11 @@ OUTS = ("x", "status", "obj", "iters", "next_states", "nb_out")
 EST_NAME = {"plain": "impc_fov_kernel<false,true>", "slack": "impc_fov_kernel<true,true>"}
 BIG = 1e4           # objectives from here on: the penalty rule
 HARD_TOL = 1e-6     # scaled violation of the hard rows (test_gpu_certify.py)
-FILTER_TOL = 1e-7   # no_cbf_filter against the filtered solve (the dual-active-set / PDIP bound)
+FILTER_TOL = ROUTE_REL  # no_cbf_filter against the filtered solve (the dual-active-set / PDIP bound)
 
 
-def _dev(torch, a, dtype=None):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=torch.device("cuda", 0))
-
-
-def _same(torch, a, b):
-    if a.is_floating_point():
-        return bool(torch.all((a == b) | (torch.isnan(a) & torch.isnan(b))))
-    return torch.equal(a, b)
-
-
-def _assert_same(torch, got, want, what, rows=None):
-    for k in OUTS:
-        a, b = (got[k], want[k]) if rows is None else (got[k][rows], want[k][rows])
-        assert _same(torch, a, b), (what, k)
-
-
-class Solver:
-    """One case on one context: the device copies of its tables and a solve that returns fresh,
-    pre-filled outputs and asserts the kernel the launch took (impc_fov_kernel<SLACK>; `kernel`:
-    another expected name, the estimate form's)."""
-
-    def __init__(self, mpclib, cfg, case, **opts):
-        self.torch = torch = _torch()
-        self.cfg = cfg
-        self.ctx = mpclib.Context(cfg, **opts)
-        self.case = c = case
-        self.states = _dev(torch, c["states"])
-        self.targets = _dev(torch, c["targets"])
-        self.rp = _dev(torch, c["rp"], torch.int32)
-        self.col = _dev(torch, c["col"] if len(c["col"]) else np.zeros(1, np.int32), torch.int32)
-
-    def solve(self, cov=None, grid=False, kernel=None):
-        torch, c, n = self.torch, self.case, self.case["num_agents"]
-        out = self.ctx.alloc_outputs(n)
-        for v in out.values():
-            v.fill_(float("nan") if v.is_floating_point() else -7)
-        out["nb_out"] = torch.full((n, 16), -7, dtype=torch.int32, device=self.states.device)
-        lists = dict(knn_k=8, knn_radius=self.cfg["fov_Rs"]) if grid else dict(nb_row_ptr=self.rp, nb_col=self.col)
-        self.ctx.impc_solve(self.states, targets=self.targets, agent_first=c["agent_first"], num_agents=n,
-                            cov=None if cov is None else _dev(torch, cov), **lists, **out)
-        torch.cuda.synchronize()
-        want = kernel or P.KERNEL["slack" if self.cfg["slack_mode"] else "plain"]
-        assert self.ctx.kernel_name == want, (self.ctx.kernel_name, want)
-        return out
-
-
-def _np(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
+# every solve asserts impc_fov_kernel<SLACK> of the setting
+Solver = functools.partial(_Solver, kernel_names=P.KERNEL)
 
 
 @functools.lru_cache(maxsize=None)
@@ -93,23 +48,8 @@ def _oracle(kind, name, setting):
 def _assert_matches_oracle(out, ref, what):
     """The suite's rule on every agent: statuses, objectives of OPTIMAL iterations, the curve of
     the last OPTIMAL iteration."""
-    g = _np(out)
-    rst, rob, rx = ref
-    worst_o = worst_x = 0.0
-    for a in range(len(rst)):
-        assert list(g["status"][a]) == list(rst[a]), (what, a, g["status"][a], rst[a])
-        last = None
-        for k in range(rst.shape[1]):
-            if rst[a, k] == O.OPTIMAL:
-                err = abs(g["obj"][a, k] - rob[a, k]) / max(1.0, abs(rob[a, k]))
-                worst_o = max(worst_o, err)
-                assert err <= OBJ_TOL, (what, a, k, g["obj"][a, k], rob[a, k])
-                last = k
-        if last is not None:
-            dx = float(np.max(np.abs(g["x"][a] - rx[a, last])))
-            worst_x = max(worst_x, dx)
-            assert dx <= X_TOL, (what, a, dx)
-    print(f"{what}: worst objective error {worst_o:.3e} (relative), worst |dx| {worst_x:.3e}")
+    g = to_host(out)
+    check_parity(g, ref, label=what)
     return g
 
 
@@ -133,7 +73,7 @@ def test_swarm_matches_oracle(mpclib, oracle, name, setting):
     if cfg["fov_beta"] <= math.pi:
         ang, rad = P.cone_margin(c, cfg["fov_beta"], cfg["fov_Rs"])
         assert ang >= 1e-9 and rad >= 1e-9  # (test_gpu_exact_geometry: no pair on a decision boundary)
-        _assert_same(s.torch, s.solve(grid=True), out, f"grid/{name}/{setting}")
+        same_bits(s.solve(grid=True), out, keys=OUTS, what=f"grid/{name}/{setting}")
 
 
 @pytest.mark.parametrize("setting", ["plain", "slack"])
@@ -144,8 +84,8 @@ def test_no_cbf_filter_changes_no_result(mpclib, name, setting):
     objectives within FILTER_TOL relative."""
     cfg = P.config(setting, **P.SWARM_CONFIGS[name])
     c = P.swarm_case(name)
-    a = _np(Solver(mpclib, cfg, c).solve())
-    b = _np(Solver(mpclib, cfg, c, no_cbf_filter=True).solve())
+    a = to_host(Solver(mpclib, cfg, c).solve())
+    b = to_host(Solver(mpclib, cfg, c, no_cbf_filter=True).solve())
     assert np.array_equal(a["status"], b["status"]), (a["status"], b["status"])
     assert int((a["status"] == O.OPTIMAL).sum()) == 66
     err = np.abs(a["obj"] - b["obj"]) / np.maximum(1.0, np.abs(a["obj"]))
@@ -174,7 +114,7 @@ def test_fans_match_oracle_and_one_over_the_cap_is_error(mpclib, oracle, name, s
     assert over["status"][n].tolist() == [O.ERROR, O.UNKNOWN]
     assert bool(s.torch.isnan(over["x"][n]).all()) and bool(s.torch.isnan(over["obj"][n]).all())
     for k in ("x", "status", "obj", "iters", "next_states"):
-        assert _same(s.torch, over[k][:n], out[k]), k
+        same_values(over[k][:n], out[k], what=k)
 
 
 @pytest.mark.parametrize("setting", ["plain", "slack"])
@@ -187,11 +127,11 @@ def test_fans_in_the_estimate_form(mpclib, name, setting):
     s = Solver(mpclib, cfg, c)
     plain = s.solve()
     assert s.ctx.kernel_name == P.KERNEL[setting]
-    nb_xy = _dev(s.torch, c["states"][c["col"], :2])
+    nb_xy = to_device(c["states"][c["col"], :2])
     s.ctx.set_fov_estimates(nb_xy, None)
     est = s.solve(kernel=EST_NAME[setting])
     assert s.ctx.kernel_name == EST_NAME[setting]
-    _assert_same(s.torch, est, plain, f"estimates/{name}/{setting}")
+    same_bits(est, plain, keys=OUTS, what=f"estimates/{name}/{setting}")
     assert int((plain["status"] == O.OPTIMAL).sum()) == 2 * c["num_agents"]
 
 
@@ -224,7 +164,7 @@ def test_row_capacity_edge_without_the_filter(mpclib, oracle, name):
     ref = P.oracle_case(cfg, c)
     rows = P.image_rows(cfg, c, 0, ref[2][0, 0], cbf_filter=False)
     assert rows[0] <= P.WROWS < rows[1] and np.all(ref[0] == O.OPTIMAL)
-    out = _np(Solver(mpclib, cfg, c, **opts).solve())
+    out = to_host(Solver(mpclib, cfg, c, **opts).solve())
     print(f"rowcap/{name}/{too_many}: rows {rows}, status {out['status'][0]}")
     assert out["status"][0].tolist() == [O.OPTIMAL, O.ERROR]
     assert abs(out["obj"][0, 0] - ref[1][0, 0]) <= OBJ_TOL * max(1.0, abs(ref[1][0, 0])) and np.isnan(out["obj"][0, 1])
@@ -232,7 +172,7 @@ def test_row_capacity_edge_without_the_filter(mpclib, oracle, name):
     assert np.max(np.abs(out["x"][0] - ref[2][0, 0])) <= X_TOL
     if name == "h2":
         # a third iteration after the ERROR: the IMPC has stopped, UNKNOWN with no objective
-        out = _np(Solver(mpclib, dict(cfg, impc_iter=3), c, **opts).solve())
+        out = to_host(Solver(mpclib, dict(cfg, impc_iter=3), c, **opts).solve())
         assert out["status"][0].tolist() == [O.OPTIMAL, O.ERROR, O.UNKNOWN] and np.all(np.isnan(out["obj"][0, 1:]))
         assert np.max(np.abs(out["x"][0] - ref[2][0, 0])) <= X_TOL
 
@@ -258,9 +198,9 @@ def test_slack_mode_with_every_box_row_has_no_room(mpclib):
     cfg = P.config("slack")
     c = P.cap_fan(1)
     assert P.slack_image_rows(cfg, 1, keep_redundant=True) > P.WROWS >= P.slack_image_rows(cfg, 8)
-    out = _np(Solver(mpclib, cfg, c, keep_redundant=True).solve())
+    out = to_host(Solver(mpclib, cfg, c, keep_redundant=True).solve())
     assert out["status"][0].tolist() == [O.ERROR, O.UNKNOWN]
-    out = _np(Solver(mpclib, cfg, c).solve())
+    out = to_host(Solver(mpclib, cfg, c).solve())
     assert out["status"][0].tolist() == [O.OPTIMAL, O.OPTIMAL]
 
 
@@ -271,8 +211,8 @@ def _device_penalty(mpclib, cfg, case, cov=None):
     violation, the QP), and the curves. The iteration-1 QP is assembled at the device's own
     iteration-0 curve, which a context with impc_iter 1 returns (its solve is iteration 0 of the
     two-iteration solve, bit for bit)."""
-    one = _np(Solver(mpclib, dict(cfg, impc_iter=1), case).solve(cov=cov))
-    two = _np(Solver(mpclib, cfg, case).solve(cov=cov))
+    one = to_host(Solver(mpclib, dict(cfg, impc_iter=1), case).solve(cov=cov))
+    two = to_host(Solver(mpclib, cfg, case).solve(cov=cov))
     assert np.array_equal(one["status"][:, 0], two["status"][:, 0])
     assert np.array_equal(one["obj"][:, 0], two["obj"][:, 0], equal_nan=True)
     p = O.make_params(cfg)

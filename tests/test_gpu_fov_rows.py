@@ -10,15 +10,15 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_oracle_fov import voronoi_kat_checks
+from gpu_harness import to_device
+from reference_kats import voronoi_kat_checks
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _dev(a):
-    import torch
-    return torch.tensor(np.asarray(a, dtype=np.float64), device="cuda")
+    return to_device(np.asarray(a, dtype=np.float64))
 
 
 def _eval(mpclib, ego, nb, fov=2.0943951023931953, Ds=0.2, Rs=6.0, bbox=(0.0, 0.0, 0.0)):

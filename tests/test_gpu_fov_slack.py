@@ -11,15 +11,16 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import fresh_outputs, require_gpu, same_bits
 from mpccbf import swarm
-from test_gpu_parity import OBJ_TOL, _torch
+from parity_rule import check_parity
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_fov_slack_closed_loop_512_agents(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     n, steps = 512, 60
     cfg = swarm.fov_config(20, slack_mode=1, slack_cost=1000.0, slack_decay_rate=0.9)
     p = O.make_params(cfg)
@@ -57,13 +58,8 @@ def test_fov_slack_closed_loop_512_agents(mpclib):
             bad = np.nonzero(np.any(st != O.OPTIMAL, axis=1))[0]
             hard = np.argsort(-it.sum(axis=1))[:16]
             agents = sorted(set(bad.tolist()) | set(hard.tolist()) | set(rng.choice(n, 24, replace=False).tolist()))
-            for a in agents:
-                r = O.impc_optimize(p, sh, a, col[rp[a]:rp[a + 1]], refs[a], covs=cov_h)
-                assert list(st[a]) == list(r["status"]), (s, a, st[a], r["status"])
-                for k in range(cfg["impc_iter"]):
-                    if r["status"][k] == O.OPTIMAL:
-                        ro = r["obj"][k]
-                        assert abs(obj[a, k] - ro) <= OBJ_TOL * max(1.0, abs(ro)), (s, a, k, obj[a, k], ro)
+            ref = [O.impc_optimize(p, sh, a, col[rp[a]:rp[a + 1]], refs[a], covs=cov_h) for a in agents]
+            check_parity(dict(status=st, obj=obj), ref, agents, label=f"step {s}", x=False)
             checked += len(agents)
         cur = out["next_states"].clone()
     assert checked >= 6 * 24 and hist[O.OPTIMAL] > 0
@@ -81,7 +77,7 @@ def test_fov_closed_loop_is_deterministic(mpclib, slack):
     LDS the active set had not written (das_wave.hpp, the slack patterns' unbounded loops): NaN /
     Inf left there by an earlier kernel turned the first direction into NaN; reproduced
     deterministically by a NaN LDS-poison build (profiles/r04_lds_poison_nan.log)."""
-    torch = _torch()
+    torch = require_gpu()
     n, steps = 512, 30
     over = dict(slack_mode=1, slack_cost=1000.0, slack_decay_rate=0.9) if slack else {}
     cfg = swarm.fov_config(20, **over)
@@ -92,9 +88,7 @@ def test_fov_closed_loop_is_deterministic(mpclib, slack):
     for fill in (float("nan"), 1.0e30):
         junk = torch.full((1 << 22,), fill, dtype=torch.float64, device=dev)  # shifts the allocator
         ctx = mpclib.Context(cfg)
-        out = ctx.alloc_outputs(n)
-        for k, v in out.items():
-            v.fill_(fill if v.dtype == torch.float64 else -7)
+        out = fresh_outputs(ctx, n, fill=(fill, -7))
         traj_t = torch.full((n,), -1.0, dtype=torch.float64, device=dev)
         out["x"].fill_(float("nan"))
         cur = torch.tensor(states, device=dev)
@@ -118,9 +112,4 @@ def test_fov_closed_loop_is_deterministic(mpclib, slack):
         del junk
     for s in range(steps):
         for a, b, name in zip(runs[0][s], runs[1][s], ("status", "iters", "obj", "next_states", "nb_out")):
-            same = torch.equal(a, b) if name != "obj" else bool(torch.all((a == b) | (torch.isnan(a) & torch.isnan(b))))
-            if not same:
-                idx = torch.nonzero(a != b)[:4].tolist()
-                vals = [(i, a[tuple(i)].item(), b[tuple(i)].item(),
-                         [runs[r][s][0][i[0]].tolist() for r in (0, 1)]) for i in idx]
-            assert same, (s, name, vals if not same else None)
+            same_bits(a, b, what=(s, name))

@@ -28,14 +28,14 @@ import functools
 import numpy as np
 import pytest
 
+from gpu_harness import require_gpu, run_oracle, to_host
 from mpccbf import swarm
-from test_gpu_parity import _torch, compare, run_oracle
+from parity_rule import check_parity, check_routes_agree
 
 pytestmark = pytest.mark.gpu
 
 N, K, RADIUS, SCALE = 64, 8, 6.0, 0.45
 SEP16 = 4
-REL = 1e-7
 MAIN = "impc_sep_kernel<1,1,false,256>"
 LEAN = "impc_sep_kernel<1,1,false,256,false,true>"
 NOISE = dict(pos_std=1e-3, vel_std=1e-3, noise_seed=11)
@@ -53,34 +53,20 @@ def _context(mpclib, lean):
     return ctx
 
 
-def _close(got, ref, what):
-    """NaN in the same places; elsewhere within REL relative. Returns the largest difference."""
-    np.testing.assert_array_equal(np.isnan(got), np.isnan(ref), err_msg=what)
-    ok = ~np.isnan(ref)
-    d = np.abs(got[ok] - ref[ok]) / np.maximum(1.0, np.abs(ref[ok]))
-    worst = float(d.max()) if d.size else 0.0
-    print(f"{what}: largest relative difference to the lean path {worst:.3e}, "
-          f"{np.count_nonzero(got[ok] != ref[ok])} of {d.size} entries differ")
-    assert worst <= REL, (what, worst)
-    return worst
-
-
 @functools.lru_cache(maxsize=None)
 def _solve(mpclib, lean):
     """One impc_solve of the scenario (computed once per path, never modified)."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     states, targets = _scenario()
     ctx = _context(mpclib, lean)
     out = ctx.alloc_outputs(N)
-    nb_out = torch.full((N, 16), -7, dtype=torch.int32, device=dev)
+    out["nb_out"] = torch.full((N, 16), -7, dtype=torch.int32, device=dev)
     ctx.impc_solve(torch.tensor(states, device=dev), targets=torch.tensor(targets, device=dev), knn_k=K,
-                   knn_radius=RADIUS, nb_out=nb_out, **out)
+                   knn_radius=RADIUS, **out)
     torch.cuda.synchronize()
     assert ctx.kernel_name == (LEAN if lean else MAIN), ctx.kernel_name
-    g = {k: v.cpu().numpy() for k, v in out.items()}
-    g["nb_out"] = nb_out.cpu().numpy()
-    return g
+    return to_host(out)
 
 
 def test_one_solve_matches_the_two_launch_lean_path(mpclib):
@@ -96,7 +82,7 @@ def test_one_solve_matches_the_two_launch_lean_path(mpclib):
     np.testing.assert_array_equal(got["iters"], ref["iters"])
     np.testing.assert_array_equal(got["nb_out"], ref["nb_out"])
     for k in ("obj", "x", "next_states"):
-        _close(got[k], ref[k], k)
+        check_routes_agree(got[k], ref[k], k + " against the lean path")
     # the three situations of the hand-over
     assert np.any(per_wave == 1), "no wave with exactly one group through the completion"
     assert np.any(per_wave >= 2), "no wave with two or more groups through the completion"
@@ -111,11 +97,11 @@ def test_one_solve_matches_the_two_launch_lean_path(mpclib):
     agents = list(range(N))
     oracle = run_oracle(cfg, states, targets, rp, col, agents)
     for g in (got, ref):
-        compare(cfg, g, oracle, agents)
+        check_parity(g, oracle, agents)
 
 
 def _loop(mpclib, lean, steps=10):
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     states, targets = _scenario()
     ctx = _context(mpclib, lean)
@@ -147,4 +133,4 @@ def test_closed_loop_matches_the_two_launch_lean_path(mpclib):
     np.testing.assert_array_equal(got["ilog"], ref["ilog"])
     np.testing.assert_array_equal(got["traj_t"], ref["traj_t"])
     for k in ("final", "x", "obj"):
-        _close(got[k], ref[k], k)
+        check_routes_agree(got[k], ref[k], k + " against the lean path")

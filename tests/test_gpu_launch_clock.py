@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conn_impc_cases import D_MAX
+from gpu_harness import require_gpu
 from mpccbf import swarm
 
 pytestmark = pytest.mark.gpu
@@ -29,16 +30,9 @@ CASES = {
 }
 
 
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
-
-
 @pytest.mark.parametrize("label", list(CASES))
 def test_clock_pairs_where_waves_and_agents_do_not_line_up(mpclib, label):
-    torch = _torch()
+    torch = require_gpu()
     cfg, variant, n, per_wave, waves, kernel, team = CASES[label]
     dev = torch.device("cuda", 0)
     states, targets = swarm.lattice_swarm(n, seed=4)
@@ -71,7 +65,7 @@ def test_clock_pairs_where_waves_and_agents_do_not_line_up(mpclib, label):
 def test_device_answers_equal_the_host_plan(mpclib, attach):
     """After one solve of 64 agents with the default variant: kernel_name and launch_waves are the
     host export's for this device's share-adaptive threshold (4 x its compute units)."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     n, cfg = 64, swarm.config(15)
     states, targets = swarm.lattice_swarm(n, seed=4)

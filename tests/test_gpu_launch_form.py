@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import launch_form_cases as L
-from test_gpu_parity import _torch
+from gpu_harness import require_gpu, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +29,7 @@ def _run(mpclib, shape, generic, calls, dual_as_steps=0):
     call after the first continues the neighbour tables), as the loop form's launch or, with nb_out
     added, as the generic form's. Returns after every call a dict of clones: the state table, x, obj,
     status, iters, traj_t, and the calls' status / iteration logs."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     _, ns, first, count = next(s for s in L.SHAPES if s[0] == shape)
     cfg = L.config()
@@ -64,21 +64,12 @@ def _run(mpclib, shape, generic, calls, dual_as_steps=0):
 
 
 def _same(got, ref):
-    torch = _torch()
+    """Every snapshot bit for bit (NaN by bit pattern: x of an agent without a curve; INFEASIBLE
+    objectives)."""
     assert len(got) == len(ref)
     for i, (g, r) in enumerate(zip(got, ref)):
-        for k in KEYS:
-            assert torch.equal(g[k], r[k]) or _nan_equal(g[k], r[k]), (i, k)
+        same_bits(g, r, keys=KEYS, what=i)
         assert not bool((g["status"] == -7).any()), i
-
-
-def _nan_equal(a, b):
-    """torch.equal with NaN equal to NaN (x of an agent without a curve; INFEASIBLE objectives):
-    the bit patterns agree."""
-    torch = _torch()
-    if not a.is_floating_point():
-        return False
-    return torch.equal(a.view(torch.int64), b.view(torch.int64))
 
 
 @pytest.mark.parametrize("shape", [s[0] for s in L.SHAPES])
@@ -89,7 +80,7 @@ def test_step_by_step_equals_the_generic_form(mpclib, shape):
     got, ref = _run(mpclib, shape, False, calls), _run(mpclib, shape, True, calls)
     _same(got, ref)
     if shape in ("n64", "sub"):
-        torch = _torch()
+        torch = require_gpu()
         st = torch.stack([g["status"][0] for g in got]).cpu().numpy()  # (steps, agents, 2)
         it = torch.stack([g["iters"][0] for g in got]).cpu().numpy()
         tt = got[0]["traj_t"].cpu().numpy()
@@ -103,19 +94,18 @@ def test_step_by_step_equals_the_generic_form(mpclib, shape):
 def test_one_call_and_a_continued_call_equal_the_generic_form(mpclib):
     """The same ten steps as one call, and as a first call of four steps and a continue_tables call
     of six: the logs of every step, and the same end as the step-by-step loop."""
-    torch = _torch()
+    require_gpu()
     for calls in ((L.STEPS,), (4, L.STEPS - 4)):
         got, ref = _run(mpclib, "n64", False, calls), _run(mpclib, "n64", True, calls)
         _same(got, ref)
         end = _run(mpclib, "n64", False, (1,) * L.STEPS)[-1]
-        for k in ("states", "x", "obj", "traj_t"):
-            assert torch.equal(got[-1][k], end[k]) or _nan_equal(got[-1][k], end[k]), (calls, k)
+        same_bits(got[-1], end, keys=("states", "x", "obj", "traj_t"), what=calls)
 
 
 def test_completion_from_the_loop_form(mpclib):
     """dual_as_steps = 1: a QP that needs a second active-set step takes impc_sep_complete, one
     function called the same way from both forms — identical statuses, step counts and values."""
-    torch = _torch()
+    torch = require_gpu()
     calls = (1,) * L.STEPS
     got = _run(mpclib, "n64", False, calls, dual_as_steps=1)
     ref = _run(mpclib, "n64", True, calls, dual_as_steps=1)

@@ -10,20 +10,15 @@ import numpy as np
 import pytest
 
 import monitor_cases as M
+from gpu_harness import require_gpu, to_device
 from mpccbf import metrics, sim, swarm
+from parity_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
 LOG_ROWS = 12
 D2_RTOL = 1e-14
 INT_KEYS = ("summary", "reached_at", "hit_samples", "unsafe_samples", "sample_log")
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
 
 
 def _monitor(mpclib, c, rows=None, **kw):
@@ -34,19 +29,19 @@ def _monitor(mpclib, c, rows=None, **kw):
 def _device_inputs(c):
     """(agents' tensor, goals, fixed table): the agents as a state table (layout "table") or as a
     n x S x 6 trace (the substeps layout); the fixed rows as the table of sample 0."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     a0, na = c["agent_first"], c["num_agents"]
     ag = c["samples"][:, a0:a0 + na]
     agents = ag[0] if c["layout"] == "table" else np.transpose(ag, (1, 0, 2))
     goals = None if c["goals"] is None else torch.tensor(c["goals"], device=dev)
     fixed = torch.tensor(c["samples"][0], device=dev) if na < c["samples"].shape[1] else None
-    return torch.tensor(np.ascontiguousarray(agents), device=dev), goals, fixed
+    return to_device(agents), goals, fixed
 
 
 def _score(mpclib, c, per_call=None, rows=None):
     """Raw outputs after a reset and the case's samples in calls of per_call samples (None: one)."""
-    torch = _torch()
+    torch = require_gpu()
     mon = _monitor(mpclib, c, rows=rows)
     agents, goals, fixed = _device_inputs(c)
     S = c["samples"].shape[0]
@@ -61,9 +56,7 @@ def _score(mpclib, c, per_call=None, rows=None):
 
 
 def _same_bits(a, b):
-    for k in INT_KEYS:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
-    np.testing.assert_array_equal(a["min_d2"].view(np.int64), b["min_d2"].view(np.int64))
+    same_bits(a, b, keys=INT_KEYS + ("min_d2",))
 
 
 @pytest.mark.parametrize("name", list(M.CASES))
@@ -88,7 +81,7 @@ def test_case_outputs(mpclib, name):
 def test_result_of_the_timing_cases(mpclib):
     for name in ("collision_before_arrival", "collision_at_arrival", "collision_after_arrival", "trace10"):
         c, _ = M.case(name)
-        torch = _torch()
+        torch = require_gpu()
         mon = _monitor(mpclib, c)
         agents, goals, fixed = _device_inputs(c)
         mon.score(agents, goals=goals)
@@ -114,7 +107,7 @@ def test_rows_beyond_the_table_stay_untouched(mpclib):
 
 
 def test_explicit_sample_first_and_reset(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     c, want = M.case("trace10")
     mon = _monitor(mpclib, c)
     agents, goals, _ = _device_inputs(c)
@@ -145,7 +138,7 @@ CROWD_N, CROWD_STEPS = 33, 12
 
 def test_simulator_monitor_equals_the_host_metrics_on_the_trace(mpclib):
     """33 agents on the crowded lattice (0.6 x the spacing), 12 steps with sub-step records."""
-    _torch()
+    require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(CROWD_N, spacing_scale=0.6)
     s = sim.Simulator(cfg, states, targets, record=True, monitor=True)
@@ -188,7 +181,7 @@ def _grid_swarm():
 
 def _run_steps(mpclib, attach, first=0, count=GRID_N):
     """GRID_STEPS grid-mode steps in one run_steps call as bench.py drives it (the loop form's options)."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     cfg, states, targets = _grid_swarm()
     ctx = mpclib.Context(cfg)
@@ -218,7 +211,7 @@ def _run_steps(mpclib, attach, first=0, count=GRID_N):
 def _solve_loop(mpclib, first=0, count=GRID_N):
     """The same steps as GRID_STEPS impc_solve calls with the monitor attached; returns the monitor's
     raw outputs and the trace of the per-step tables (rows x steps x 6)."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     cfg, states, targets = _grid_swarm()
     ctx = mpclib.Context(cfg)
@@ -250,9 +243,7 @@ def test_run_steps_is_untouched_by_the_monitor(mpclib):
     assert plain["form"] == watched["form"] == "loop"
     assert plain["name"] == watched["name"]
     for k in ("final", "x", "obj", "status", "iters", "traj_t"):
-        np.testing.assert_array_equal(plain[k].view(np.int64) if plain[k].dtype == np.float64 else plain[k],
-                                      watched[k].view(np.int64) if watched[k].dtype == np.float64 else watched[k],
-                                      err_msg=k)
+        same_bits(watched[k], plain[k], what=k)
     assert not (watched["status"] == -7).any()
     assert raw["summary"][0] == GRID_STEPS
 
@@ -281,7 +272,7 @@ def test_run_steps_with_fixed_rows_equals_the_solve_loop(mpclib):
 
 
 def test_detach_and_refusals(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     cfg, states, targets = _grid_swarm()
     ctx = mpclib.Context(cfg)

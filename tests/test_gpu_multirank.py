@@ -14,16 +14,10 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_harness import require_gpu
 from mpccbf import swarm
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
 
 
 def _run(mpclib, torch, cfg, states, targets, steps, nranks, cov=None, variant=None, names=None):
@@ -80,7 +74,7 @@ def test_local_group_matches_single_rank(mpclib, nranks, n_agents, variant):
     variant 0 (share-adaptive): every rank's 1024 agents take the one-agent-per-wave kernel, so
     the single-rank loop is run with that kernel forced (variant 5) and the two must agree bit for
     bit; variant 4: the 16-lane kernel on both sides."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(n_agents, seed=13)
     states[:, :2] *= 0.6  # crowded: CBF rows, infeasible QPs, fallback trajectories
@@ -106,7 +100,7 @@ def test_local_group_fov_config5_shape(mpclib, slack):
     cone-filtered neighbour query over the gathered table, foreign rows inserted after the
     exchange), with and without slack variables: bit-identical to the single-rank closed loop,
     solver-step counts included."""
-    torch = _torch()
+    torch = require_gpu()
     over = dict(slack_mode=1, slack_cost=1000.0, slack_decay_rate=0.9) if slack else {}
     cfg = swarm.fov_config(20, **over)
     states, targets = swarm.heading_swarm(4096)
@@ -127,7 +121,7 @@ def test_local_group_fov_config5_shape(mpclib, slack):
 def test_local_group_rank_failure_does_not_hang(mpclib):
     """A rank whose mpccbf_run_steps disagrees (a different num_steps) or fails aborts the
     in-process group: every rank returns an error instead of waiting at a barrier forever."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(256, seed=3)
     dev = torch.device("cuda", 0)

@@ -16,7 +16,8 @@ import exact_geometry_cases as X
 import neighbour_shortcut_cases as S
 import oracle_lib as O
 from mpccbf import swarm
-from test_gpu_parity import _torch, compare, run_oracle
+from gpu_harness import require_gpu, run_oracle, to_host
+from parity_rule import check_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +38,7 @@ def _ctx(mpclib, name):
 
 
 def _solve(mpclib, name, states, targets, k, radius):
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     ctx = _ctx(mpclib, name)
     n = len(states)
@@ -47,7 +48,7 @@ def _solve(mpclib, name, states, targets, k, radius):
                    targets=torch.tensor(targets, dtype=torch.float64, device=dev), knn_k=k, knn_radius=radius,
                    nb_out=nbo, **out)
     torch.cuda.synchronize()
-    g = {key: v.cpu().numpy() for key, v in out.items()}
+    g = to_host(out)
     g["nb_out"] = nbo.cpu().numpy()
     g["kernel"] = ctx.kernel_name
     return g
@@ -80,7 +81,7 @@ def test_nb_out_equals_cpu_lists(mpclib, query):
 
 def test_solve_matches_oracle(mpclib):
     """The solve lattice (waves without a ranked group and waves that mix both), every agent,
-    against the oracle on the CPU lists: test_gpu_parity.compare's statuses and tolerances."""
+    against the oracle on the CPU lists: parity_rule.check_parity's statuses and tolerances."""
     cfg = swarm.config(15)
     st, tg = S.solve_lattice()
     k, r = S.SOLVE_QUERY
@@ -91,4 +92,4 @@ def test_solve_matches_oracle(mpclib):
     for name in ("sep16", "dense16"):
         g = _solve(mpclib, name, st, tg, k, r)
         np.testing.assert_array_equal(g["nb_out"], X.padded(rp, col), err_msg=name)
-        compare(cfg, g, ref, agents)
+        check_parity(g, ref, agents)

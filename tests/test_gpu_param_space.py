@@ -11,8 +11,9 @@ import pytest
 import oracle_lib as O
 import param_space_cases as C
 from mpccbf import swarm
+from gpu_harness import fresh_outputs, require_gpu, run_gpu, run_oracle, to_host
 from mpccbf._lib import MpccbfError
-from test_gpu_parity import _torch, compare, run_gpu, run_oracle
+from parity_rule import check_parity, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +47,7 @@ def check_variants(mpclib, torch, cfg, st, tg, rp, col, ref, names, refs=None, *
             ctx.set_variant(variant)
         g = run_gpu(ctx, st, tg, rp, col, torch, refs=refs)
         assert ctx.kernel_name == name, (variant, ctx.kernel_name)
-        compare(cfg, g, ref, agents)
+        check_parity(g, ref, agents)
 
 
 def lattice():
@@ -63,12 +64,10 @@ def solve(ctx, torch, st, rp=None, col=None, **kw):
     ctx.impc_solve(t(st), t(rp), t(col), **{k: (t(v) if isinstance(v, np.ndarray) else v) for k, v in kw.items()},
                    **out)
     torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return to_host(out)
 
 
-def assert_same_bits(a, b, keys=("status", "obj", "x", "iters", "next_states")):
-    for k in keys:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+OUT_KEYS = ("status", "obj", "x", "iters", "next_states")
 
 
 # ---- 1. reference trajectories ------------------------------------------------------------------
@@ -80,7 +79,7 @@ def test_refs_match_oracle(mpclib, spd_f):
     of 8, a multiple, and more than the 10 constant lanes of a 16-lane group take in two passes.
     The one-agent-per-wave kernel still applies at spd_f = 15 (hot operator prefix 1,952 <= 2,048
     doubles)."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = lattice()
     cfg = swarm.config(15, spd_f=spd_f)
     refs = C.moving_refs(st, tg, 15, cfg["h"], 7)
@@ -91,7 +90,7 @@ def test_refs_match_oracle(mpclib, spd_f):
 def test_refs_fov_and_slack_match_oracle(mpclib):
     """refs through the FoV kernel (G = 64 lanes of the constant's striding) and the collision
     slack kernel, spd_f = 5 (nr = 15)."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.fov_config(20, spd_f=5)
     st, tg = C.fov_swarm()
     rp, col = swarm.fov_csr(st, 8, cfg["fov_Rs"], cfg["fov_beta"])
@@ -110,7 +109,7 @@ def test_refs_fov_and_slack_match_oracle(mpclib):
 def test_refs_of_replicated_target_equal_targets_call(mpclib, variant):
     """refs = the target replicated over the horizon is the targets= call's problem: the same
     statuses, objectives within 1e-10 relative (Qr r sums the entries Qt t holds pre-summed)."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = lattice()
     cfg = swarm.config(15)
     ctx = mpclib.Context(cfg)
@@ -128,7 +127,7 @@ def test_refs_of_replicated_target_equal_targets_call(mpclib, variant):
 def test_refs_entries_before_the_tail_are_not_read(mpclib, spd_f):
     """Only the last spd_f samples of refs enter the cost: 1e6 in every earlier entry leaves every
     output bit-identical (collision layouts and the FoV kernel)."""
-    torch = _torch()
+    torch = require_gpu()
     for fov in (False, True):
         if fov:
             cfg = swarm.fov_config(20, spd_f=spd_f)
@@ -149,14 +148,14 @@ def test_refs_entries_before_the_tail_are_not_read(mpclib, spd_f):
             b = run_gpu(ctx, st, tg, rp, col, torch, refs=head)
             assert ctx.kernel_name == (FOV if fov else NAMES[variant])
             assert np.count_nonzero(a["status"][:, 0] == O.OPTIMAL) >= 50
-            assert_same_bits(a, b)
+            same_bits(a, b, keys=OUT_KEYS)
 
 
 @pytest.mark.parametrize("variant", [3, 4, 5])
 def test_refs_are_indexed_by_the_batch_local_agent(mpclib, variant):
     """agent_first = 12, num_agents = 40 with a 40-row refs equals rows 12 .. 51 of the full solve
     bit for bit: row i of refs belongs to agent agent_first + i."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = lattice()
     cfg = swarm.config(15, spd_f=3)
     refs = C.moving_refs(st, tg, 15, cfg["h"], 7)
@@ -170,7 +169,7 @@ def test_refs_are_indexed_by_the_batch_local_agent(mpclib, variant):
     part = solve(ctx, torch, st, rp[12:53].copy(), col, refs=buf[:40], agent_first=12, num_agents=40)
     assert ctx.kernel_name == NAMES[variant]
     assert np.count_nonzero(full["status"][12:52, 0] == O.OPTIMAL) >= 20
-    assert_same_bits({k: v[12:52] for k, v in full.items()}, part)
+    same_bits({k: v[12:52] for k, v in full.items()}, part, keys=OUT_KEYS)
 
 
 def _loop_with_refs(ctx, torch, st0, steps, **kw):
@@ -191,7 +190,7 @@ def _loop_with_refs(ctx, torch, st0, steps, **kw):
 
 def test_run_steps_with_refs_matches_step_by_step(mpclib):
     """mpccbf_run_steps with refs over 3 steps == three impc_solve calls, bit for bit."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     st, tg, _, _ = lattice()
     cfg = swarm.config(15, spd_f=3)
@@ -205,8 +204,8 @@ def test_run_steps_with_refs_matches_step_by_step(mpclib):
     r = ctx.run_steps(a, b, 3, refs=refs, knn_k=8, knn_radius=6.0, x=out["x"], obj=out["obj"], status_log=log)
     torch.cuda.synchronize()
     assert ctx.kernel_name == WIDE
-    np.testing.assert_array_equal(r["final"].cpu().numpy(), ref_states)
-    np.testing.assert_array_equal(log.cpu().numpy(), ref_log)
+    same_bits(r["final"].cpu().numpy(), ref_states)
+    same_bits(log.cpu().numpy(), ref_log)
     assert np.count_nonzero(ref_log[:, :, 0] == O.OPTIMAL) > 64
 
 
@@ -219,7 +218,7 @@ def test_cbf_horizon_lattice_matches_oracle(mpclib, cbf_h):
     108 doubles per CBF sample: 2,024 at cbf_horizon = 5 still fits the one-agent-per-wave kernel's
     2,048, 2,348 at 8 does not — there the default falls back to the 16-lane kernel and variant 5
     (not a 16-lane variant) to the dense 64-lane instantiation."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = lattice()
     cfg = swarm.config(15, cbf_horizon=cbf_h)
     names = {4: SEP, 5: WIDE, 0: WIDE} if cbf_h < 8 else {4: SEP, 5: DENSE64, 0: SEP}
@@ -230,7 +229,7 @@ def test_cbf_horizon_lattice_matches_oracle(mpclib, cbf_h):
 def test_cbf_horizon_3_grid_mode_equals_csr(mpclib):
     """Grid mode with 8 neighbours starts deferring at cbf_horizon = 3 (8 x 3 > 16 row slots,
     impc_launch_plan): the grid solve equals the CSR solve on the same lists."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = lattice()
     cfg = swarm.config(15, cbf_horizon=3)
     for variant in (4, 5):
@@ -242,7 +241,7 @@ def test_cbf_horizon_3_grid_mode_equals_csr(mpclib):
         np.testing.assert_array_equal(g["status"], g_csr["status"])
         ok = g["status"] == O.OPTIMAL
         np.testing.assert_allclose(g["obj"][ok], g_csr["obj"][ok], rtol=1e-10, atol=1e-9)
-        compare(cfg, g, oracle_ref(("cbf_h", 3), cfg, st, tg, rp, col), list(range(64)))
+        check_parity(g, oracle_ref(("cbf_h", 3), cfg, st, tg, rp, col), list(range(64)))
 
 
 @pytest.mark.parametrize("n_ring,cbf_h", [(12, 8), (20, 4), (40, 3)])
@@ -252,7 +251,7 @@ def test_ring_iteration1_rows_use_the_capacity_launch(mpclib, n_ring, cbf_h):
     capacity launch's 128: no ERROR, parity for every agent. (At cbf_horizon = 8 the operators do
     not fit the one-agent-per-wave kernel: the default is the 16-lane kernel, and variant 5 the
     dense 64-lane instantiation, which holds the rows itself.)"""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15, cbf_horizon=cbf_h)
     st, tg, rp, col = C.ring(n_ring)
     ref = oracle_ref(("ring", n_ring, cbf_h), cfg, st, tg, rp, col)
@@ -263,7 +262,7 @@ def test_ring_iteration1_rows_use_the_capacity_launch(mpclib, n_ring, cbf_h):
         g = run_gpu(ctx, st, tg, rp, col, torch)
         assert ctx.kernel_name == name
         assert not np.any(g["status"] == O.ERROR), np.argwhere(g["status"] == O.ERROR)[:5]
-        compare(cfg, g, ref, list(range(n_ring + 1)))
+        check_parity(g, ref, list(range(n_ring + 1)))
 
 
 def test_ring_beyond_the_capacity_launch_reports_error(mpclib):
@@ -271,7 +270,7 @@ def test_ring_beyond_the_capacity_launch_reports_error(mpclib):
     capacity launch's 128 (include/mpccbf.h: beyond that the QP reports ERROR). Agent 0:
     [OPTIMAL, ERROR], x the iteration-0 curve (the last OPTIMAL iteration's); every other agent as
     the oracle has it."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15, cbf_horizon=5)
     st, tg, rp, col = C.ring(40)
     ref = oracle_ref(("ring", 40, 5), cfg, st, tg, rp, col)
@@ -285,22 +284,20 @@ def test_ring_beyond_the_capacity_launch_reports_error(mpclib):
         assert abs(g["obj"][0, 0] - ro) <= 1e-4 * max(1.0, abs(ro))
         assert np.max(np.abs(g["x"][0] - ref[0]["x"][0][:36])) <= 1e-5
         others = list(range(1, 41))
-        compare(cfg, {k: v[1:] for k, v in g.items()}, [ref[i] for i in others], list(range(40)))
+        check_parity({k: v[1:] for k, v in g.items()}, [ref[i] for i in others], list(range(40)))
 
 
 def test_slack_mode_beyond_cbf_horizon_2_is_a_clean_error(mpclib):
     """Collision slack mode with cbf_horizon = 3 has no kernel (a neighbour's lane holds two
     samples' rows): the solve returns MPCCBF_ERR_CAPACITY (-3) with a message and launches
     nothing — the outputs keep their sentinel — and the library goes on working."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     cfg = swarm.config(15, slack_mode=1, cbf_horizon=3)
     st, tg, rp, col = lattice()
     ctx = mpclib.Context(cfg)
     assert ctx.kernel_name == ""
-    out = ctx.alloc_outputs(64)
-    for v in out.values():
-        v.fill_(-77)
+    out = fresh_outputs(ctx, 64, fill=-77)
     with pytest.raises(MpccbfError) as e:
         ctx.impc_solve(torch.tensor(st, device=dev), torch.tensor(rp, device=dev), torch.tensor(col, device=dev),
                        targets=torch.tensor(tg, device=dev), **out)
@@ -318,7 +315,7 @@ def test_fov_slack_mode_beyond_cbf_horizon_2_is_refused_at_create(mpclib):
     """The FoV controller refuses slack_mode with cbf_horizon = 3 earlier still: mpccbf_create
     returns MPCCBF_ERR_INVALID_ARGUMENT (-1) with a message naming the limit, so there is no
     context to solve with (launch_impc_fov's own check is never reached)."""
-    _torch()
+    require_gpu()
     cfg = swarm.fov_config(20, slack_mode=1, slack_cost=1000.0, cbf_horizon=3)
     with pytest.raises(MpccbfError) as e:
         mpclib.Context(cfg)
@@ -331,7 +328,7 @@ def test_fov_slack_mode_beyond_cbf_horizon_2_is_refused_at_create(mpclib):
 def test_fov_cbf_horizon_matches_oracle(mpclib, cbf_h):
     """FoV controller without slack at cbf_horizon 1 and 3, the full observed-neighbour lists (at
     most 3 observed neighbours here: 4 kinds x 3 x 3 rows stay within the kernel's rows)."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.fov_config(20, cbf_horizon=cbf_h)
     st, tg = C.fov_swarm()
     rp, col = swarm.fov_csr(st, 8, cfg["fov_Rs"], cfg["fov_beta"])
@@ -340,15 +337,6 @@ def test_fov_cbf_horizon_matches_oracle(mpclib, cbf_h):
 
 
 # ---- 3. IMPC iterations -------------------------------------------------------------------------
-
-def _guarded_outputs(ctx, n, torch, guard=8):
-    """Outputs of n agents as the leading rows of buffers `guard` rows longer, all filled with a
-    sentinel: (the views to pass, the full buffers)."""
-    full = ctx.alloc_outputs(n + guard)
-    for v in full.values():
-        v.fill_(-77)
-    return {k: v[:n] for k, v in full.items()}, full
-
 
 def _cases_iter(impc_iter):
     st, tg, rp, col = lattice()
@@ -367,7 +355,7 @@ def test_impc_iter_outputs_and_parity(mpclib, impc_iter):
     """impc_iter 1, 3 and 4 (outputs indexed ai * impc_iter + it; the one-agent-per-wave kernel
     writes iterations >= 2 as they finish): every entry of the n x impc_iter outputs is written,
     nothing past their end, parity with the oracle, x the last OPTIMAL iteration's curve."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     for tag, cfg, st, tg, rp, col, names in _cases_iter(impc_iter):
         ref = oracle_ref(("iter", tag, impc_iter), cfg, st, tg, rp, col)
@@ -376,23 +364,23 @@ def test_impc_iter_outputs_and_parity(mpclib, impc_iter):
             ctx = mpclib.Context(cfg)
             if variant:
                 ctx.set_variant(variant)
-            out, full = _guarded_outputs(ctx, n, torch)
+            out, full = fresh_outputs(ctx, n, guard=8, fill=-77)
             assert out["status"].shape == (n, impc_iter) and out["obj"].shape == (n, impc_iter)
             ctx.impc_solve(torch.tensor(st, device=dev), torch.tensor(rp, device=dev), torch.tensor(col, device=dev),
                            targets=torch.tensor(tg, device=dev), **out)
             torch.cuda.synchronize()
             assert ctx.kernel_name == name, (tag, variant, ctx.kernel_name)
-            g = {k: v.cpu().numpy() for k, v in full.items()}
+            g = to_host(full)
             for k, v in g.items():
                 assert np.all(v[n:] == -77), (tag, variant, k)  # the guard rows
                 assert not np.any(v[:n] == -77), (tag, variant, k, np.argwhere(v[:n] == -77)[:4])
-            compare(cfg, {k: v[:n] for k, v in g.items()}, ref, list(range(n)))
+            check_parity({k: v[:n] for k, v in g.items()}, ref, list(range(n)))
 
 
 def test_run_steps_impc_iter_3_matches_step_by_step(mpclib):
     """3 native closed-loop steps with impc_iter = 3 and a status_log (count x impc_iter per
     step) == the step-by-step loop, bit for bit."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     st, tg, _, _ = lattice()
     cfg = swarm.config(15, impc_iter=3)
@@ -407,9 +395,9 @@ def test_run_steps_impc_iter_3_matches_step_by_step(mpclib):
                       status_log=log[:3], iters_log=ilog[:3])
     torch.cuda.synchronize()
     assert ctx.kernel_name == WIDE
-    np.testing.assert_array_equal(r["final"].cpu().numpy(), ref_states)
+    same_bits(r["final"].cpu().numpy(), ref_states)
     lg = log.cpu().numpy()
-    np.testing.assert_array_equal(lg[:3], ref_log)
+    same_bits(lg[:3], ref_log)
     assert np.all(lg[3] == -9) and np.all(ilog.cpu().numpy()[3] == -9)  # nothing past 3 steps' logs
     assert not np.any(ilog.cpu().numpy()[:3] == -9)
     assert np.count_nonzero(np.all(ref_log == O.OPTIMAL, axis=2)) > 64
@@ -430,7 +418,7 @@ def test_yaw_and_asymmetric_limits_match_oracle(mpclib, rate):
     (ASYM). rate 0.9: all OPTIMAL, 27 / 14 / 20 agents with a tight box row in x / y / yaw.
     rate 2.4: 24 agents' yaw rate lies below v_min[2], infeasible by the constant rows of the yaw
     channel alone, 40 OPTIMAL. All layouts and collision slack mode."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = _yaw_case(rate)
     cfg = swarm.config(15, **C.ASYM)
     check_variants(mpclib, torch, cfg, st, tg, rp, col, oracle_ref(("yaw", rate), cfg, st, tg, rp, col), NAMES)
@@ -446,7 +434,7 @@ def test_cbf_filter_uses_each_channels_own_bound(mpclib):
     other side's narrower bound would drop the row and return another curve. (A wider wrong bound
     only keeps more rows, which changes no result: the collision rows' yaw coefficient is 0, so
     which bound channel 2 reads cannot show.)"""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = C.filter_edge()
     cfg = swarm.config(15, **C.ASYM)
     ref = oracle_ref("filter edge", cfg, st, tg, rp, col)
@@ -458,7 +446,7 @@ def test_cbf_filter_uses_each_channels_own_bound(mpclib):
 
 
 def test_fov_asymmetric_limits_match_oracle(mpclib):
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.fov_config(20, **C.ASYM)
     st, tg = C.fov_swarm()
     rp, col = swarm.fov_csr(st, 8, cfg["fov_Rs"], cfg["fov_beta"])
@@ -470,7 +458,7 @@ def test_fov_asymmetric_limits_match_oracle(mpclib):
 def test_combined_case_matches_oracle(mpclib):
     """ASYM limits, cbf_horizon = 3, impc_iter = 3, spd_f = 5, moving refs and yaw (rate 2.4) at
     once: 39 x all OPTIMAL, 24 x INFEASIBLE, 1 x (OPTIMAL, INFEASIBLE, -)."""
-    torch = _torch()
+    torch = require_gpu()
     st, tg, rp, col = _yaw_case(2.4)
     cfg = swarm.config(15, cbf_horizon=3, impc_iter=3, spd_f=5, **C.ASYM)
     refs = C.moving_refs(st, tg, 15, cfg["h"], 7)
@@ -496,7 +484,7 @@ def _reduction_case(mpclib, torch, k_hor, name, variant=0, **opts):
     assert ok.sum() >= 120
     err = np.abs(g["obj"][ok] - base["obj"][ok]) / np.maximum(1.0, np.abs(base["obj"][ok]))
     assert err.max() <= 1e-8, err.max()
-    compare(cfg, g, ref, list(range(64)))
+    check_parity(g, ref, list(range(64)))
 
 
 @pytest.mark.parametrize("k_hor,name", [(10, DENSE16), (15, DENSE64)])
@@ -507,12 +495,12 @@ def test_keep_redundant_changes_no_result(mpclib, k_hor, name):
     capacity launch). `name` is what variant 3 runs: impc_kernel<6,16,4> below 64 rows (these
     inputs' at most 4 live rows fit its 7 slots), impc_kernel<6,64,4> from 64 on. Each: same
     statuses as the default context, objectives within 1e-8 relative, parity with the oracle."""
-    _reduction_case(mpclib, _torch(), k_hor, DENSE64, keep_redundant=True)
-    _reduction_case(mpclib, _torch(), k_hor, name, variant=3, keep_redundant=True)
+    _reduction_case(mpclib, require_gpu(), k_hor, DENSE64, keep_redundant=True)
+    _reduction_case(mpclib, require_gpu(), k_hor, name, variant=3, keep_redundant=True)
 
 
 @pytest.mark.parametrize("k_hor", [10, 15])
 def test_no_cbf_filter_changes_no_result(mpclib, k_hor):
     """mpccbf_options.no_cbf_filter: every CBF row staged (8 neighbours x 2 samples = the 16 slots
     at most); the rows the filter drops are implied by the box rows, so nothing changes."""
-    _reduction_case(mpclib, _torch(), k_hor, WIDE, no_cbf_filter=True)
+    _reduction_case(mpclib, require_gpu(), k_hor, WIDE, no_cbf_filter=True)

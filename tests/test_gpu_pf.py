@@ -15,18 +15,12 @@ import pytest
 import oracle_lib as O
 import pf_cases
 import pf_ref
+from gpu_harness import require_gpu
 from mpccbf import swarm
 
 pytestmark = pytest.mark.gpu
 
 CASES = {c["name"]: c for c in pf_cases.all_cases()}
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +44,7 @@ class Dev:
     """A case's tensors on the device; init / step through the C ABI, results read back as numpy."""
 
     def __init__(self, mpclib, case, fill=0.0):
-        torch = _torch()
+        torch = require_gpu()
         self.lib, self.c, self.torch = mpclib, case, torch
         self.dev = torch.device("cuda", 0)
         self.p = _c_params(mpclib, case["par"])
@@ -229,7 +223,7 @@ def _slack_cfg(decay=0.5):
 def test_estimates_feed_the_fov_controller(mpclib):
     """est_xy / est_cov of a stepped FovEstimator straight into fov_control_solve in slack mode,
     against the oracle on the same estimates (tolerances of tests/test_fov_control.py's slack test)."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = _slack_cfg()
     n = 64
     states, targets = swarm.heading_swarm(n, seed=5)
@@ -268,7 +262,7 @@ def test_fov_control_loop_against_the_reference_chain(mpclib):
     """3 robots, 30 steps, no noise; at every step the reference chain on the device's inputs of that
     step: pf_ref from the device's particle state, the FovControl oracle on the device's estimates,
     the double-integrator update and the yaw wrap. Robot 2 turns past +pi."""
-    _torch()
+    require_gpu()
     cfg = _slack_cfg(0.1)
     # a triangle whose robots face its inside, so each keeps the two others in view; robot 2 looks
     # along -x (yaw 3.05, turning at 0.8 rad/s) and its goal yaw -3.0 is closest as -3.0 + 2 pi

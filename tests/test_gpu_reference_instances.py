@@ -10,16 +10,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import require_gpu
 from mpccbf import instances, sim
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
 
 
 # (first OPTIMAL -> INFEASIBLE transition of an iteration-0 QP in the 400-step runs,
@@ -39,7 +33,7 @@ TRANSITIONS = {("2r/circle", "base"): 11, ("5r/circle", "base"): 2, ("6r/circle"
 def test_reference_instance_gauss_seidel_matches_oracle(mpclib, name, mode, steps):
     """mode "base": the reference's run (base_config.json overlaid); "own": the instance file's own
     parameters (d_min 0.8, w_u_eff 1, ...), the keys it lacks from the base config."""
-    _torch()
+    require_gpu()
     cfg, states, targets, shape, kind, noise = instances.instance(name, preprocess=mode)
     seed = 20251015
     s = sim.Simulator(cfg, states, targets, neighbours="all", order="gauss_seidel", record=False,

@@ -8,20 +8,14 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import require_gpu
 from mpccbf import metrics, sim, swarm
 
 pytestmark = pytest.mark.gpu
 
 
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
-
-
 def test_states_json_trace_and_metrics(mpclib, tmp_path):
-    _torch()
+    require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(36, seed=4)
     s = sim.Simulator(cfg, states, targets, neighbours="all", pos_std=1e-3, vel_std=1e-2, noise_seed=3)
@@ -57,7 +51,7 @@ def test_states_json_trace_and_metrics(mpclib, tmp_path):
 
 def test_substeps_follow_the_kept_curve(mpclib):
     """Without noise every sub-step record is the kept curve at traj_t + Ts k (oracle curve eval)."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states, targets = swarm.lattice_swarm(16, seed=8)
     s = sim.Simulator(cfg, states, targets, neighbours="all")
@@ -77,7 +71,7 @@ def test_hold_position_noise_accumulates_over_substeps(mpclib):
     """Robots with no trajectory yet hold their position at zero velocity, each of the h / Ts
     sub-steps adding noise to the previous one (example :210-216): position variance nsub
     pos_std^2, velocity variance vel_std^2."""
-    _torch()
+    require_gpu()
     cfg = swarm.config(15)
     n = 4096
     states, targets = swarm.lattice_swarm(n, seed=2)
@@ -106,7 +100,7 @@ def test_gauss_seidel_trace_matches_oracle(mpclib, neighbours):
     table as it stood at its turn) and every IMPC status equal; the free-running oracle loop stays
     within 1e-4 over the 30 steps (differences at rounding level grow through the CBF rows: Bc is
     cubic in the distance margin)."""
-    _torch()
+    require_gpu()
     cfg = swarm.config(15)
     n, steps = (64, 30) if neighbours == "knn" else (24, 20)
     states, targets = swarm.lattice_swarm(n, seed=21)
@@ -160,7 +154,7 @@ def test_next_state_same_with_and_without_substeps(mpclib):
     the sub-step records are requested, so one closed loop is bit-reproducible across output
     options; the last sub-step record is that next state, and without noise it is the kept curve at
     h (oracle Bernstein evaluation of the device's control points) within 1e-9."""
-    torch = _torch()
+    torch = require_gpu()
     dev = torch.device("cuda", 0)
     cfg = swarm.config(15)
     n = 256

@@ -15,20 +15,13 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import require_gpu, to_host
 from mpccbf import swarm
+from parity_rule import check_parity
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OBJ_TOL = 1e-4
-X_TOL = 1e-5
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test needs a visible MI355X")
-    return torch
 
 
 def _check_agents(cfg, states, targets, agents, g_status, g_obj, g_x=None, cov=None, lists=None):
@@ -36,25 +29,17 @@ def _check_agents(cfg, states, targets, agents, g_status, g_obj, g_x=None, cov=N
     p = O.make_params(cfg)
     refs = swarm.refs_from_targets(targets, cfg["k_hor"])
     rp, col = swarm.knn_csr(states, 8, 3.0 * cfg["d_min"])
+    ref = {}
     for a in agents:
         nb = lists[a] if lists is not None else col[rp[a]:rp[a + 1]]
-        r = O.impc_optimize(p, states, a, nb, refs[a], covs=cov)
-        assert list(g_status[a]) == list(r["status"]), (a, g_status[a], r["status"])
-        for it in range(cfg["impc_iter"]):
-            if r["status"][it] == O.OPTIMAL:
-                ro = r["obj"][it]
-                assert abs(g_obj[a, it] - ro) <= OBJ_TOL * max(1.0, abs(ro)), (a, it, g_obj[a, it], ro)
-        if g_x is not None:
-            last = [it for it in range(cfg["impc_iter"]) if r["status"][it] == O.OPTIMAL]
-            if last:
-                xr = r["x"][last[-1]][:g_x.shape[1]]
-                assert np.max(np.abs(g_x[a] - xr)) <= X_TOL, (a, np.max(np.abs(g_x[a] - xr)))
+        ref[int(a)] = O.impc_optimize(p, states, a, nb, refs[a], covs=cov)
+    check_parity(dict(status=g_status, obj=g_obj, x=g_x), ref, agents, x=g_x is not None)
 
 
 def test_regression_cases_match_oracle(mpclib):
     """Captured instances that once failed (tests/golden/regress_cases.json): agent 0 against its
     listed neighbours, the GPU's statuses / objectives / control points against the oracle."""
-    torch = _torch()
+    torch = require_gpu()
     cases = json.load(open(os.path.join(HERE, "golden", "regress_cases.json")))["cases"]
     # (records beyond the oracle's reach are held by the penalty objective in test_gpu_fov_params.py)
     cases = [c for c in cases if c.get("reference") != "penalty"]
@@ -83,7 +68,7 @@ def test_regression_cases_match_oracle(mpclib):
                        torch.tensor(col, device=dev), targets=torch.tensor(targets[:1], device=dev),
                        num_agents=1, cov=None if cov is None else torch.tensor(cov, device=dev), **out)
         torch.cuda.synchronize()
-        g = {k: v.cpu().numpy() for k, v in out.items()}
+        g = to_host(out)
         _check_agents(cfg, states, targets, [0], g["status"], g["obj"], g["x"], cov=cov,
                       lists={0: np.arange(1, n, dtype=np.int32)})
 
@@ -97,7 +82,7 @@ def test_bench_workload_statuses_match_oracle(mpclib, n, snaps, kernel):
     """Every non-OPTIMAL agent and a seeded sample of 256 OPTIMAL ones of the closed-loop-evolved
     swarm against the oracle, at the launch size of config 3 (the 16-lane kernel) and of config
     4's rank share (the default variant's one-agent-per-wave kernel)."""
-    torch = _torch()
+    torch = require_gpu()
     cfg = swarm.config(15)
     states_h, targets_h = swarm.lattice_swarm(n)
     dev = torch.device("cuda", 0)

@@ -902,6 +902,92 @@ typedef struct mpccbf_formation_batch {
 int mpccbf_formation_rollout(const mpccbf_connectivity_control_params* p, const mpccbf_formation_params* f,
                              const mpccbf_formation_batch* b, int32_t device, void* hip_stream);
 
+/* ---- MPC-CBF team rollouts in the example's order (feature macro; MPCCBF_ABI_VERSION is unchanged:
+ * no struct changed layout) -----------------------------------------------------------------------
+ *
+ * The closed loop of mpc_cbf/examples/MPCCBFFormationControl_example.cpp:131-231 for a batch of
+ * independent teams (<= 16 robots each), one wavefront per team, the whole loop on the device, with
+ * the context's operators. Per step, robot by robot in index order (robots before it have already
+ * moved, :140, :201): ConnectivityIMPCCBF::optimize against every other robot of the team in index
+ * order, read from the team's table as it stands (the pipeline of mpccbf_impc_solve's dense 64 x 4
+ * layout, impc_kernel<6,64,4>: both IMPC iterations, iteration 1 only after an OPTIMAL iteration 0,
+ * the kept curve the last OPTIMAL iteration's); then the closed-loop semantics of mpccbf_batch.traj_t:
+ * a new curve resets traj_t to 0; with a kept curve, nsub = int(h / Ts) sub-steps at traj_t + Ts k
+ * clamped to the curve's range; with no curve yet the robot holds its position at zero velocity, the
+ * sub-steps' noise accumulating (:208-221). The noise is pos_std / vel_std times normal_sample(
+ * team_seed[t], absolute step, robot's index in its team, component, sub-step), a pure function of
+ * those, so a team's run depends on nothing but its own seed and data: not on its place in the batch,
+ * nor on how the steps are split over launches and calls. A team alone with team_seed = noise_seed is
+ * the loop of one mpccbf_impc_solve per robot (agent_first = i, num_agents = 1, next_states written
+ * back in place) with all-others lists.
+ *
+ * Carried between steps, launches and calls, in/out, initialised by the caller: states; x_keep
+ * (robots x n, n = mpccbf_num_vars: the kept curves, NaN = none); traj_t (robots, -1 = none); the
+ * summary. Records (optional, per decision, [num_steps][robots] rows in the order of `states`, robots
+ * = team_ptr[num_teams]): status, obj, iters (x impc_iter each, as mpccbf_batch's), x (the kept curve
+ * after the decision), traj_t0 (traj_t as the decision found it), substeps (nsub x 6: the states the
+ * example writes to states.json; the last one is the robot's new row), trace (the table after the
+ * step).
+ * Summary (optional, in/out so that calls chain; the caller initialises -1 / +inf / 0), scored as
+ * experiments/python/metrics/collision_check.py scores a states.json over the sub-step samples,
+ * sample number step * nsub + k, after the last robot of the step has moved: arrival_sample,
+ * first_collision, min_d2 as mpccbf_formation_batch's; fail_count = the decisions without an OPTIMAL
+ * iteration.
+ *
+ * Asynchronous: it enqueues ceil(num_steps / steps_per_launch) launches on the stream
+ * (steps_per_launch 0 = MPCCBF_TEAM_STEPS_PER_LAUNCH) and returns; the results do not depend on the
+ * split. The context keeps a device copy of the all-others lists and, when substeps is not recorded,
+ * one step's sub-step rows; both are allocated at the first call that needs them (a growth
+ * synchronises the device). An attached active-set store, monitor or neighbour-cap audit is not
+ * consulted. A team of more than 16 robots takes no step: every decision of it reports MPCCBF_ERROR
+ * (later iterations UNKNOWN, NaN obj), its states stay, its x, traj_t0, substeps and trace rows copy
+ * what it has, its fail_count counts them all. An empty team writes nothing.
+ * Refused with MPCCBF_ERR_INVALID_ARGUMENT on the host, before any launch (mpccbf_last_error names
+ * the reason): a NULL argument; a FoV context (cbf_mode 1); slack_mode; operators the dense 64 x 4
+ * layout does not take (reduced dimension != 6, 256 or more shared rows); 15 * cbf_horizon > 256 -
+ * shared rows (a full team's CBF rows would not fit: no team of 1 .. 16 can meet a capacity error in
+ * the kernel); a context with connectivity rows attached (a context is never bound to a communicator:
+ * mpccbf_run_steps alone takes one, so the rollout is single-rank by construction); negative or
+ * non-finite pos_std, vel_std or goal_radius, shape_half not positive and finite, steps_per_launch
+ * < 0, negative num_teams, num_steps or step_first, step_first + num_steps beyond 2^31 - 1, with
+ * arrival_sample or first_collision given (step_first + num_steps) * nsub beyond 2^31 - 1 (their
+ * sample numbers are int32), and with teams and steps to run a NULL team_ptr, states, targets,
+ * team_seed, x_keep or traj_t. num_teams == 0 or num_steps == 0: MPCCBF_OK, nothing enqueued. */
+#define MPCCBF_HAS_TEAM_ROLLOUT 1
+#define MPCCBF_TEAM_STEPS_PER_LAUNCH 2
+typedef struct mpccbf_team_rollout_params {
+    double pos_std, vel_std;
+    double shape_half[2];      /* the box's half extents as collision_check.py takes them */
+    double goal_radius;        /* as given (the script's default is 1.0); 0: only a robot on its target */
+    int32_t steps_per_launch;  /* 0 = MPCCBF_TEAM_STEPS_PER_LAUNCH */
+} mpccbf_team_rollout_params;
+
+typedef struct mpccbf_team_batch {
+    int32_t num_teams;
+    const int32_t* team_ptr;    /* num_teams + 1 offsets into the robot rows */
+    double* states;             /* robots x 6, in/out: the table after the last step */
+    const double* targets;      /* robots x 3 */
+    const uint64_t* team_seed;  /* num_teams */
+    int64_t step_first;         /* absolute index of the first step (noise key, sample numbers) */
+    int32_t num_steps;
+    double* x_keep;             /* in/out, robots x n: the kept curves (NaN: none) */
+    double* traj_t;             /* in/out, robots: the kept curve's evaluation time (-1: none) */
+    int32_t* status;            /* out, [num_steps][robots][impc_iter], or NULL */
+    double* obj;                /* out, [num_steps][robots][impc_iter], or NULL */
+    int32_t* iters;             /* out, [num_steps][robots][impc_iter], or NULL */
+    double* x;                  /* out, [num_steps][robots][n], or NULL */
+    double* traj_t0;            /* out, [num_steps][robots], or NULL */
+    double* substeps;           /* out, [num_steps][robots][nsub][6], or NULL */
+    double* trace;              /* out, [num_steps][robots][6], or NULL */
+    int32_t* arrival_sample;    /* in/out, robots (-1: not yet), or NULL */
+    int32_t* first_collision;   /* in/out, num_teams x 3 (sample, i, j; -1: none), or NULL */
+    double* min_d2;             /* in/out, num_teams (+inf), or NULL */
+    int32_t* fail_count;        /* in/out, num_teams, or NULL */
+} mpccbf_team_batch;
+
+int mpccbf_team_rollout(mpccbf_ctx* ctx, const mpccbf_team_rollout_params* p, const mpccbf_team_batch* b,
+                        void* hip_stream);
+
 /* Generic dense QP in the flattened CPLEX form (host pointers; synchronous):
  *   minimise  x^T H x + c^T x + c0        (H symmetric: sum_{i<=j} q_ij x_i x_j, CPLEX.cpp:122-147)
  *   s.t.      lo_r <= A_r x <= hi_r       (rows; lo == hi is an equality)

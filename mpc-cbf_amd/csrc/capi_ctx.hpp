@@ -132,6 +132,9 @@ struct mpccbf_ctx {
         bool on = false;
         mpccbf_monitor m{};
     } mon;
+    // team rollouts (mpccbf_team_rollout): the all-others lists of every team size (team_lists,
+    // uploaded at the first call) and, for calls that do not record the sub-steps, one step's rows
+    mpccbf::DevBuf team_lists, team_work;
 };
 
 namespace mpccbf {

@@ -14,21 +14,15 @@
 namespace mpccbf {
 namespace dev {
 
+// One agent of the dense layout on its group of G lanes (gl: the lane in the group), from the state
+// load through write_agent_outputs: what impc_kernel runs per group and team_rollout_kernel
+// (team_rollout.hip) per robot turn. stage: the group's cap * (NZ + 1) doubles of LDS for the CBF
+// rows, cap = R * G - op.m; nbs: the group's scratch of the grid query. Returns whether the agent
+// has a new curve (an OPTIMAL iteration).
 template <int NZ, int G, int R>
-__global__ void __launch_bounds__(256) impc_kernel(const DevOps op, const double* __restrict__ buf,
-                                                    const ImpcArgs args) {
-    constexpr int GPB = 256 / G;
-    const int gl = threadIdx.x & (G - 1);
-    const int gib = threadIdx.x / G;
-    const int ai = blockIdx.x * GPB + gib;  // agent index within the batch
-    grid_clear<256>(args);
-    if (ai >= args.num_agents) return;      // whole group leaves together
-    stamp(args, ai, gl, 0);
-
-    extern __shared__ double lds_stage[];
+__device__ __forceinline__ bool impc_dense_agent(const DevOps& op, const double* buf, const ImpcArgs& args,
+                                                 int ai, int gl, double* stage, NbScratch& nbs) {
     const int cap = R * G - op.m;  // CBF row slots per agent
-    double* stage = lds_stage + (size_t)gib * cap * (NZ + 1);
-
     const int self = args.agent_first + ai;
     double s0[6];
 #pragma unroll
@@ -68,16 +62,15 @@ __global__ void __launch_bounds__(256) impc_kernel(const DevOps op, const double
     // k nearest within the radius from the spatial hash (3 x 3 cells around the agent)
     const bool grid_mode = args.nb_row_ptr == nullptr;
     int nb0 = 0, nnb = 0;
-    __shared__ NbScratch nb_scratch[GPB];
     if (!grid_mode) {
         nb0 = args.nb_row_ptr[ai];
         nnb = args.nb_row_ptr[ai + 1] - nb0;
     } else {
-        nnb = grid_neighbors<G>(args, self, s0[0], s0[1], nb_scratch[gib], gl);
+        nnb = grid_neighbors<G>(args, self, s0[0], s0[1], nbs, gl);
     }
     const bool nb_overflow = nnb < 0;
     if (nb_overflow) nnb = 0;
-    write_nb_out(args, ai, gl, grid_mode, nb_scratch[gib], nb0, nnb);
+    write_nb_out(args, ai, gl, grid_mode, nbs, nb0, nnb);
     stamp(args, ai, gl, 2);
 
     double y[NZ], ykeep[NZ];
@@ -93,7 +86,7 @@ __global__ void __launch_bounds__(256) impc_kernel(const DevOps op, const double
             continue;
         }
         bool row_infeasible = false;
-        const int count = stage_cbf_rows<NZ, G>(op, buf, args, it, s0, y, grid_mode, &nb_scratch[gib],
+        const int count = stage_cbf_rows<NZ, G>(op, buf, args, it, s0, y, grid_mode, &nbs,
                                                 nb0, nnb, stage, cap, gl, &row_infeasible);
         if (it < 2) stamp(args, ai, gl, 3 + 2 * it);
         // ---- CBF rows into the free slots (previous iteration's CBF rows are replaced)
@@ -159,6 +152,24 @@ __global__ void __launch_bounds__(256) impc_kernel(const DevOps op, const double
     }
     write_agent_outputs<NZ, G>(op, buf, args, ai, gl, s0, ykeep, have_curve);
     stamp(args, ai, gl, 7);
+    return have_curve;
+}
+
+template <int NZ, int G, int R>
+__global__ void __launch_bounds__(256) impc_kernel(const DevOps op, const double* __restrict__ buf,
+                                                    const ImpcArgs args) {
+    constexpr int GPB = 256 / G;
+    const int gl = threadIdx.x & (G - 1);
+    const int gib = threadIdx.x / G;
+    const int ai = blockIdx.x * GPB + gib;  // agent index within the batch
+    grid_clear<256>(args);
+    if (ai >= args.num_agents) return;      // whole group leaves together
+    stamp(args, ai, gl, 0);
+
+    extern __shared__ double lds_stage[];
+    __shared__ NbScratch nb_scratch[GPB];
+    double* stage = lds_stage + (size_t)gib * (R * G - op.m) * (NZ + 1);
+    impc_dense_agent<NZ, G, R>(op, buf, args, ai, gl, stage, nb_scratch[gib]);
 }
 
 }  // namespace dev

@@ -16,6 +16,8 @@ from . import monitor  # noqa: F401
 from .monitor import SafetyMonitor  # noqa: F401
 from . import formation  # noqa: F401
 from .formation import FormationRollouts  # noqa: F401
+from . import team_rollout  # noqa: F401  (the binding's function is _lib.team_rollout)
+from .team_rollout import TeamRollouts  # noqa: F401
 from .estimator import FovEstimator  # noqa: F401
 from .fov_control_sim import FovControlLoop  # noqa: F401
 from .fov_impc_sim import FovImpcLoop  # noqa: F401

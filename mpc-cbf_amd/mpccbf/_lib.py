@@ -27,7 +27,7 @@ EXPORTED = [
     "mpccbf_host_launch_plan", "mpccbf_pf_init", "mpccbf_pf_step", "mpccbf_launch_form",
     "mpccbf_host_launch_form", "mpccbf_set_fov_estimates", "mpccbf_monitor_scratch_bytes",
     "mpccbf_monitor_table_size", "mpccbf_monitor_reset", "mpccbf_monitor_score", "mpccbf_set_monitor",
-    "mpccbf_formation_rollout",
+    "mpccbf_formation_rollout", "mpccbf_team_rollout",
 ]
 
 # ImpcKernel ids (csrc/kernels/launch_plan.hpp) of the 16-lane main launch: generic and loop form
@@ -297,6 +297,8 @@ def load():
     if hasattr(L, "mpccbf_formation_rollout"):  # (MPCCBF_LIB may name a library from before the rollouts)
         L.mpccbf_formation_rollout.argtypes = [C.POINTER(ConnControlParams), C.POINTER(FormationParams),
                                                C.POINTER(FormationBatch), C.c_int32, vp]
+    if hasattr(L, "mpccbf_team_rollout"):  # (MPCCBF_LIB may name a library from before the team rollouts)
+        L.mpccbf_team_rollout.argtypes = [vp, C.POINTER(TeamRolloutParams), C.POINTER(TeamBatch), vp]
     _lib = L
     return L
 
@@ -1046,6 +1048,51 @@ def formation_rollout(cfg: dict, team_ptr, states, targets, team_seed, num_steps
     if not hasattr(L, "mpccbf_formation_rollout"):
         raise MpccbfError(f"{LIB_PATH} has no mpccbf_formation_rollout (a library from before the rollouts)")
     _check(L.mpccbf_formation_rollout(C.byref(p), C.byref(f), C.byref(b), int(device), _stream(stream)))
+
+
+TEAM_STEPS_PER_LAUNCH = 2  # MPCCBF_TEAM_STEPS_PER_LAUNCH
+
+
+class TeamRolloutParams(C.Structure):
+    _fields_ = [("pos_std", C.c_double), ("vel_std", C.c_double), ("shape_half", C.c_double * 2),
+                ("goal_radius", C.c_double), ("steps_per_launch", C.c_int32)]
+
+
+class TeamBatch(C.Structure):
+    _fields_ = [("num_teams", C.c_int32), ("team_ptr", C.c_void_p), ("states", C.c_void_p),
+                ("targets", C.c_void_p), ("team_seed", C.c_void_p), ("step_first", C.c_int64),
+                ("num_steps", C.c_int32), ("x_keep", C.c_void_p), ("traj_t", C.c_void_p),
+                ("status", C.c_void_p), ("obj", C.c_void_p), ("iters", C.c_void_p), ("x", C.c_void_p),
+                ("traj_t0", C.c_void_p), ("substeps", C.c_void_p), ("trace", C.c_void_p),
+                ("arrival_sample", C.c_void_p), ("first_collision", C.c_void_p), ("min_d2", C.c_void_p),
+                ("fail_count", C.c_void_p)]
+
+
+def team_rollout(ctx, team_ptr, states, targets, team_seed, x_keep, traj_t, num_steps: int, step_first: int = 0, *,
+                 pos_std: float = 0.0, vel_std: float = 0.0, shape_half=(0.2, 0.2), goal_radius: float = 1.0,
+                 steps_per_launch: int = 0, status=None, obj=None, iters=None, x=None, traj_t0=None,
+                 substeps=None, trace=None, arrival_sample=None, first_collision=None, min_d2=None,
+                 fail_count=None, stream=None):
+    """The MPC-CBF example's closed loop for a batch of teams on the device (mpccbf_team_rollout) with
+    the operators of the Context `ctx`: num_steps steps from step_first, robots in index order.
+    Device tensors: team_ptr (int32, teams + 1), states (robots x 6, in/out), targets (robots x 3),
+    team_seed (int64 holding the uint64 seeds' bits, teams), x_keep (robots x ctx.n, in/out, NaN = no
+    curve), traj_t (robots, in/out, -1 = none); the optional records [num_steps][robots][.] and the
+    in/out summary (arrival_sample int32 robots, first_collision int32 teams x 3, min_d2 float64
+    teams, fail_count int32 teams)."""
+    p = TeamRolloutParams(pos_std=pos_std, vel_std=vel_std, goal_radius=goal_radius,
+                          steps_per_launch=int(steps_per_launch))
+    p.shape_half[0], p.shape_half[1] = float(shape_half[0]), float(shape_half[1])
+    b = TeamBatch(num_teams=team_ptr.shape[0] - 1, team_ptr=_ptr(team_ptr), states=_ptr(states),
+                  targets=_ptr(targets), team_seed=_ptr(team_seed), step_first=int(step_first),
+                  num_steps=int(num_steps), x_keep=_ptr(x_keep), traj_t=_ptr(traj_t), status=_ptr(status),
+                  obj=_ptr(obj), iters=_ptr(iters), x=_ptr(x), traj_t0=_ptr(traj_t0), substeps=_ptr(substeps),
+                  trace=_ptr(trace), arrival_sample=_ptr(arrival_sample), first_collision=_ptr(first_collision),
+                  min_d2=_ptr(min_d2), fail_count=_ptr(fail_count))
+    L = load()
+    if not hasattr(L, "mpccbf_team_rollout"):
+        raise MpccbfError(f"{LIB_PATH} has no mpccbf_team_rollout (a library from before the team rollouts)")
+    _check(L.mpccbf_team_rollout(ctx._h, C.byref(p), C.byref(b), _stream(stream)))
 
 
 def comm_unique_id() -> bytes:

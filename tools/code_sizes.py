@@ -24,7 +24,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-u
          "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 SRCS = ["csrc/kernels/impc_kernel.hip", "csrc/kernels/impc_store.hip", "csrc/kernels/impc_conn.hip",
         "csrc/kernels/impc_fov.hip", "csrc/kernels/impc_fov_est.hip", "csrc/kernels/connectivity_control.hip",
-        "csrc/dense_qp.hip"]
+        "csrc/dense_qp.hip", "csrc/kernels/team_rollout.hip"]
 
 
 def device_code(src):

@@ -13,7 +13,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "mpc-cbf_amd")
 SRCS = ["csrc/kernels/impc_kernel.hip", "csrc/kernels/impc_store.hip", "csrc/kernels/impc_conn.hip",
         "csrc/kernels/impc_fov.hip", "csrc/kernels/impc_fov_est.hip", "csrc/kernels/cbf_control.hip",
-        "csrc/kernels/connectivity_control.hip", "csrc/kernels/formation_rollout.hip", "csrc/kernels/neighbors.hip", "csrc/kernels/cap_audit.hip",
+        "csrc/kernels/connectivity_control.hip", "csrc/kernels/formation_rollout.hip", "csrc/kernels/team_rollout.hip",
+        "csrc/kernels/neighbors.hip", "csrc/kernels/cap_audit.hip",
         "csrc/dense_qp.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
          "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form"]

@@ -131,7 +131,7 @@ __device__ __forceinline__ bool impc_dense_agent(const DevOps& op, const double*
             if (st != ST_OPTIMAL) {
                 // certify: minimal uniform row violation above the feasibility tolerance
                 const double tstar = pdip_phase1<NZ, G, R>(rw, cfg);
-                if (tstar > op.feas_tol) {
+                if (tstar > op.feas_tol && tstar < 1e300) {  // (1e300: phase 1 failed, the PDIP decides)
                     st = ST_INFEASIBLE;
                     prs = tstar;
                 }

@@ -758,7 +758,12 @@ __device__ __forceinline__ void impc_sep_agent(const DevOps& op, const double* _
                 }
             }
             st = po.status;
-            nit = total + tr_p1;  // active-set, PDIP and phase-1 steps
+            // active-set and PDIP steps. Phase 1's steps are not counted (include/mpccbf.h): it
+            // starts from the failed solve's last iterate and stops as soon as its decision is
+            // settled, so its count depends on that iterate's last bits — the in-kernel completion
+            // and the fallback launch, two code objects of this source, took 7 and 9 steps to the
+            // same t* (test_gpu_feasibility.py, test_lean_step_counts).
+            nit = total;
             if (gl == 0) res[0] = st == ST_INFEASIBLE ? tstar : po.rp, res[1] = po.rd;
 #ifdef MPCCBF_SOLVE_TRACE  // diagnostics build: warm + 100 cold + 10000 phase-1 iterations
             nit = tr_warm + 100 * tr_cold + 10000 * tr_p1;
